@@ -14,7 +14,15 @@ precision (PyTorch-1.9-era fp32 training; nothing is reduced).
 
 Contract: --gpus N --steps K --warmup W; W untimed rounds, then
 barrier+synchronize, K timed rounds, barrier+synchronize; elapsed is the
-MAX over ranks; rank 0 prints one JSON line."""
+MAX over ranks; rank 0 prints one JSON line.
+
+A plain run does only that: set up, warm up, time the K rounds, print the
+result line.  --dump-outputs DIR additionally writes what the last timed
+round produced (see dump_outputs) so two builds can be compared output for
+output; every input is derived from the fixed default seed, so the same
+arguments give the same inputs on every run.  --full is the switch for
+any measurement beyond the headline figure; the benchmark has none at
+present, so it changes nothing."""
 
 import argparse
 import json
@@ -22,6 +30,27 @@ import os
 import time
 
 import torch
+
+
+def dump_outputs(out_dir, world_state, sampled):
+    """Write what the last timed round handed back as DIR/<name>.npy:
+    the global model it left behind (flat fp32 parameters, plus the flat
+    BatchNorm buffers when the model has any) and the agent ids it
+    aggregated, in sampled order.  The largest model here (ResNet18,
+    11.2 M fp32 parameters = 45 MB) stays under the 64 MB cap."""
+    import numpy as np
+    gm = world_state['global_model']
+    arrays = {
+        'global_params': gm.flat_params.detach().float().cpu().numpy(),
+        'sampled_agents': np.asarray(sampled, dtype=np.float64),
+    }
+    if gm.n_buffers:
+        arrays['global_buffers'] = \
+            gm.flat_buffers.detach().float().cpu().numpy()
+    assert sum(v.nbytes for v in arrays.values()) <= 64 * 2 ** 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f'{name}.npy'), arr)
 
 
 def main():
@@ -39,7 +68,14 @@ def main():
                     choices=['fp32', 'bf16'],
                     help="client compute dtype; the headline FMNIST config "
                          "is fp32 (the reference's own precision)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="after the timed steps, write the last step's "
+                         "outputs as DIR/<name>.npy")
+    ap.add_argument('--full', action='store_true',
+                    help="also run every measurement beyond the headline "
+                         "figure (none at present)")
     a = ap.parse_args()
+    assert a.steps >= 1, "--steps must be at least 1"
 
     from rlr_amd.federated import build_world, run_round
     from rlr_amd.options import default_args
@@ -77,7 +113,7 @@ def main():
     sync()
     t0 = time.perf_counter()
     for rnd in range(a.warmup + 1, a.warmup + a.steps + 1):
-        run_round(args, world_state, rnd, rank, n)
+        sampled = run_round(args, world_state, rnd, rank, n)
     sync()
     elapsed = time.perf_counter() - t0
 
@@ -89,6 +125,8 @@ def main():
     elapsed_max = float(t.item())
 
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, world_state, sampled)
         value = a.steps / elapsed_max
         out = {
             "metric": "fl_rounds_per_sec",
