@@ -5,7 +5,10 @@ Re-implements, MI355X-first, the capabilities of the AAAI-2021 reference
 `TinfoilHat0/Defending-Against-Backdoors-with-Robust-Learning-Rate`
 (see SURVEY.md): federated training of K agents under pixel-pattern trojan
 attacks, with FedAvg / coordinate-median / sign aggregation modulated by the
-per-parameter robust-learning-rate sign vote.
+per-parameter robust-learning-rate sign vote.  Build addition: the
+coordinate-wise trimmed mean (--aggr trmean, Yin et al. 2018), sharing one
+LDS sorting-network kernel family with the median at more than 64 sampled
+agents.
 
 Architecture (nothing here is a port):
   * one process per GPU; sampled agents are sharded contiguously across

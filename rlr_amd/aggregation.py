@@ -15,7 +15,16 @@ Rules (each a HIP kernel on the GPU path, ops/csrc/aggregation.hip):
   * FedAvg (aggregation.py:57-64): sum_k n_k U_k / sum_k n_k, fp64, summed
     in sampled order for world-size-invariant bitwise results.
   * coordinate median (aggregation.py:66-69): torch.median column semantics
-    (lower of the two middle values for even K).
+    (lower of the two middle values for even K).  K <= 64 runs the
+    count-and-pick kernel; larger K sorts each column in LDS
+    (ops/csrc/orderstat.hip) and selects the same element.
+  * coordinate-wise trimmed mean (build addition, --aggr trmean; Yin et
+    al., 2018): unweighted like the median; per coordinate drop
+    b = floor(trim_frac * K) values from each end of the sorted column and
+    average the rest, summed sequentially in ascending order in fp64 —
+    agent-order invariant and bitwise equal between CPU and GPU.
+    Without noise, trmean (and comed above K = 64) take ONE fused kernel:
+    LDS sort + sign vote from the resident tile + fp32 apply.
   * sign (aggregation.py:71-75): sign(sum_k sign(U_k)).
   * optional N(0, noise*clip) gaussian noise (aggregation.py:34-35) from a
     per-round derived stream.  NOTE: the fused GPU avg path draws noise
@@ -77,6 +86,24 @@ class Aggregation:
                 float(noise_std), seed, 0, False)
             return
 
+        if _gpu(stacked) and self.args.noise == 0:
+            # order-statistic rules: ONE fused kernel sorts each column in
+            # LDS, takes the vote from the resident tile and applies
+            K = stacked.shape[0]
+            span = None
+            if self.args.aggr == 'trmean':
+                b = self._trim_count(K)
+                span = (b, K - b)
+            elif self.args.aggr == 'comed' and K > 64:
+                span = ((K - 1) // 2, (K - 1) // 2 + 1)
+            if span is not None and K <= ext().orderstat_max_k():
+                ext().orderstat_rlr_apply(
+                    stacked, span[0], span[1], global_model.flat_params,
+                    self.args.robustLR_threshold > 0,
+                    float(self.args.robustLR_threshold),
+                    float(self.server_lr), False)
+                return
+
         lr_vector = None
         if self.args.robustLR_threshold > 0:
             lr_vector = self.compute_robustLR(stacked)
@@ -85,6 +112,8 @@ class Aggregation:
             agg = self.agg_avg(stacked, agent_ids)
         elif self.args.aggr == 'comed':
             agg = self.agg_comed(stacked)
+        elif self.args.aggr == 'trmean':
+            agg = self.agg_trmean(stacked)
         elif self.args.aggr == 'sign':
             agg = self.agg_sign(stacked)
         else:
@@ -124,11 +153,46 @@ class Aggregation:
         return out / w.sum()
 
     def agg_comed(self, stacked):
-        # the register-select kernel holds one column of K values per lane;
-        # beyond K=64 fall back to torch.median on device (same semantics)
-        if _gpu(stacked) and stacked.shape[0] <= 64:
-            return ext().agg_comed(stacked)
+        # the count-and-pick kernel re-reads the column K times per value
+        # and is bound to K <= 64; above that the LDS sorting kernel selects
+        # the same element (a median is a selection, so bitwise identical);
+        # beyond its K limit fall back to torch.median (same semantics)
+        K = stacked.shape[0]
+        if _gpu(stacked):
+            if K <= 64:
+                return ext().agg_comed(stacked)
+            if K <= ext().orderstat_max_k():
+                m = (K - 1) // 2
+                return ext().agg_orderstat(stacked, m, m + 1, False,
+                                           0.0, 0.0)[0]
         return torch.median(stacked, dim=0).values
+
+    def _trim_count(self, K):
+        """b = floor(trim_frac * K) values dropped from each end."""
+        b = int(self.args.trim_frac * K)
+        if K - 2 * b < 1:
+            raise ValueError(
+                f"trim_frac={self.args.trim_frac} trims {b} of K={K} sampled "
+                f"agents from each end and leaves nothing to average")
+        return b
+
+    def agg_trmean(self, stacked):
+        """Coordinate-wise trimmed mean (Yin et al., 2018), unweighted like
+        comed: per coordinate sort the K values, drop b from each end and
+        average the rest.  The kept values are summed sequentially in
+        ASCENDING order in fp64 and multiplied by 1/(K-2b) — the HIP kernel
+        does exactly this, so CPU and GPU agree bit for bit and the result
+        does not depend on the agent order."""
+        K = stacked.shape[0]
+        b = self._trim_count(K)
+        if _gpu(stacked) and K <= ext().orderstat_max_k():
+            return ext().agg_orderstat(stacked, b, K - b, False, 0.0, 0.0)[0]
+        kept = torch.sort(stacked, dim=0).values[b:K - b]
+        out = torch.zeros(stacked.shape[1], dtype=torch.float64,
+                          device=stacked.device)
+        for r in range(K - 2 * b):
+            out += kept[r]
+        return out * (1.0 / (K - 2 * b))
 
     def agg_sign(self, stacked):
         if _gpu(stacked):

@@ -117,6 +117,12 @@ void launch_agg_comed(const double*, int, long, double*, void*);
 void launch_apply_update(float*, const double*, const double*, double, long,
                          void*);
 void launch_add_noise(double*, double, long, uint64_t, uint64_t, void*);
+// orderstat.hip
+int orderstat_max_k();
+void launch_agg_orderstat(const double*, int, long, int, int, double, double*,
+                          double*, double, double, void*);
+void launch_orderstat_rlr_apply(const double*, int, long, int, int, double,
+                                int, double, double, float*, double*, void*);
 // gemm_f32.hip
 int gemm_f32_splitk(int, int, int);
 void launch_gemm_f32(const float*, const float*, float*, const float*,
@@ -685,6 +691,54 @@ torch::Tensor agg_comed(torch::Tensor U) {
   launch_agg_comed(U.data_ptr<double>(), U.size(0), U.size(1),
                    out.data_ptr<double>(), stream_of(U));
   return out;
+}
+
+// Shared argument checks of the order-statistic entry points: (K, n) fp64,
+// contiguous, on device, 1 <= K <= orderstat_max_k(), 0 <= lo < hi <= K.
+static void check_orderstat(const torch::Tensor& U, int64_t lo, int64_t hi) {
+  CHK(U.is_cuda());
+  CHK(U.dim() == 2);
+  CHK(U.scalar_type() == torch::kFloat64);
+  CHK(U.is_contiguous());
+  CHK(U.size(0) >= 1 && U.size(0) <= orderstat_max_k());
+  CHK(U.size(1) >= 1);
+  CHK(0 <= lo && lo < hi && hi <= U.size(0));
+}
+
+std::tuple<torch::Tensor, torch::Tensor> agg_orderstat(
+    torch::Tensor U, int64_t lo, int64_t hi, bool want_lr, double thresh,
+    double slr) {
+  check_orderstat(U, lo, hi);
+  int K = U.size(0);
+  long n = U.size(1);
+  auto out = torch::empty({n}, U.options());
+  auto lr = want_lr ? torch::empty({n}, U.options())
+                    : torch::empty({0}, U.options());
+  launch_agg_orderstat(U.data_ptr<double>(), K, n, (int)lo, (int)hi,
+                       1.0 / (double)(hi - lo), out.data_ptr<double>(),
+                       want_lr ? lr.data_ptr<double>() : nullptr, thresh, slr,
+                       stream_of(U));
+  return {out, lr};
+}
+
+torch::Tensor orderstat_rlr_apply(torch::Tensor U, int64_t lo, int64_t hi,
+                                  torch::Tensor params, bool rlr,
+                                  double thresh, double slr, bool want_lr) {
+  check_orderstat(U, lo, hi);
+  CHK(params.is_cuda() && params.is_contiguous());
+  CHK(params.device() == U.device());
+  CHK(params.scalar_type() == torch::kFloat32);
+  CHK(params.numel() == U.size(1));
+  int K = U.size(0);
+  long n = U.size(1);
+  auto lr = want_lr ? torch::empty({n}, U.options())
+                    : torch::empty({0}, U.options());
+  launch_orderstat_rlr_apply(U.data_ptr<double>(), K, n, (int)lo, (int)hi,
+                             1.0 / (double)(hi - lo), rlr ? 1 : 0, thresh,
+                             slr, params.data_ptr<float>(),
+                             want_lr ? lr.data_ptr<double>() : nullptr,
+                             stream_of(U));
+  return lr;
 }
 
 void apply_update(torch::Tensor params, torch::Tensor agg, torch::Tensor lr,
@@ -1391,6 +1445,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("agg_sign", &agg_sign);
   m.def("agg_comed", &agg_comed);
   m.def("apply_update", &apply_update);
+  m.def("agg_orderstat", &agg_orderstat);
+  m.def("orderstat_rlr_apply", &orderstat_rlr_apply);
+  m.def("orderstat_max_k", []() { return orderstat_max_k(); });
   m.def("add_noise", &add_noise);
   m.def("gemm", &gemm);
   m.def("gemm_bf16", &gemm_bf16);

@@ -28,8 +28,8 @@ def args_parser(argv=None):
     parser.add_argument('--rounds', type=int, default=200,
                         help="number of communication rounds R")
     parser.add_argument('--aggr', type=str, default='avg',
-                        choices=['avg', 'comed', 'sign'],
-                        help="aggregation rule")
+                        choices=['avg', 'comed', 'sign', 'trmean'],
+                        help="aggregation rule (trmean is a build addition)")
     parser.add_argument('--local_ep', type=int, default=2,
                         help="number of local epochs E")
     parser.add_argument('--bs', type=int, default=256,
@@ -65,6 +65,9 @@ def args_parser(argv=None):
                              "keeps datasets resident in HBM and does not use workers)")
 
     # ---- MI355X build additions ----
+    parser.add_argument('--trim_frac', type=float, default=0.1,
+                        help="fraction of sampled agents trimmed from each "
+                             "end per coordinate (--aggr trmean)")
     parser.add_argument('--seed', type=int, default=42,
                         help="master seed; all RNG streams derive from it "
                              "world-size-invariantly")
@@ -97,13 +100,20 @@ def args_parser(argv=None):
                         help="TensorBoard log root")
 
     args = parser.parse_args(argv)
-    return finalize_args(args)
+    try:
+        return finalize_args(args)
+    except ValueError as e:
+        parser.error(str(e))
 
 
 def finalize_args(args):
     """Derived rules. server_lr forced to 1 unless aggr=='sign'
-    (reference federated.py:23)."""
+    (reference federated.py:23); 0 <= trim_frac < 0.5 so that at least one
+    value per coordinate survives the trim for every K."""
     args.server_lr = args.server_lr if args.aggr == 'sign' else 1.0
+    if not 0 <= args.trim_frac < 0.5:
+        raise ValueError(
+            f"--trim_frac must be in [0, 0.5), got {args.trim_frac}")
     if args.device is None:
         import torch
         if torch.cuda.is_available():

@@ -7,11 +7,16 @@ from time import ctime
 
 
 def run_name(args):
-    """Reference federated.py:27-30 run-name string."""
-    return (f"time:{ctime()}-clip_val:{args.clip}-noise_std:{args.noise}"
+    """Reference federated.py:27-30 run-name string; the trimmed mean (a
+    build addition) appends its trim fraction, every other rule keeps the
+    reference name byte for byte."""
+    name = (f"time:{ctime()}-clip_val:{args.clip}-noise_std:{args.noise}"
             f"-aggr:{args.aggr}-s_lr:{args.server_lr}-num_cor:{args.num_corrupt}"
             f"thrs_robustLR:{args.robustLR_threshold}"
             f"-num_corrupt:{args.num_corrupt}-pttrn:{args.pattern_type}")
+    if args.aggr == 'trmean':
+        name += f"-trim:{args.trim_frac}"
+    return name
 
 
 def build_writer(args):
@@ -30,6 +35,8 @@ def print_exp_details(args):
     print(f'    Dataset: {args.data}')
     print(f'    Global Rounds: {args.rounds}')
     print(f'    Aggregation Function: {args.aggr}')
+    if args.aggr == 'trmean':
+        print(f'    Trim Fraction: {args.trim_frac}')
     print(f'    Number of agents: {args.num_agents}')
     print(f'    Fraction of agents: {args.agent_frac}')
     print(f'    Batch size: {args.bs}')
