@@ -164,6 +164,7 @@ void launch_conv_bwd_weight_bf16(const unsigned short*,
 int conv_bwdw_tap_ok(int, int, int, int, int, int, int, int);
 int conv_bwdw_tap_s2_ok(int, int, int, int, int, int, int, int);
 int conv_bwdw_tap_slabs(int, int, int);
+int conv_bwdw_tap_ws_slabs(int, int, int, int*, int*, int*);
 void launch_conv_bwdw_tap_s2_bf16(const unsigned short*,
                                   const unsigned short*, float*, float*,
                                   int, int, int, int, int, void*);
@@ -983,9 +984,10 @@ static void bf16_dw(const torch::Tensor& dy, const torch::Tensor& x,
                     int Nb, int C, int H, int W, int Kout, int R, int S,
                     int stride, int pad, void* st) {
   if (conv_bwdw_tap_ok(C, H, W, Kout, R, S, stride, pad)) {
-    int SL = conv_bwdw_tap_slabs(Nb, C, Kout);
-    // +16 slabs: scratch for the two-stage combine's chunk sums
-    auto ws = torch::empty({(long)(SL + 16) * Kout * C * 9},
+    // image-group slabs + the two-stage combine's chunk sums, exactly as
+    // the launcher lays them out
+    int SL = conv_bwdw_tap_ws_slabs(Nb, C, Kout, nullptr, nullptr, nullptr);
+    auto ws = torch::empty({(long)SL * Kout * C * 9},
                            w.options().dtype(torch::kFloat));
     launch_conv_bwdw_tap_bf16((const unsigned short*)dy.data_ptr(),
                               (const unsigned short*)x.data_ptr(),
@@ -994,8 +996,8 @@ static void bf16_dw(const torch::Tensor& dy, const torch::Tensor& x,
     return;
   }
   if (conv_bwdw_tap_s2_ok(C, H, W, Kout, R, S, stride, pad)) {
-    int SL = conv_bwdw_tap_slabs(Nb, C, Kout);
-    auto ws = torch::empty({(long)(SL + 16) * Kout * C * 9},
+    int SL = conv_bwdw_tap_ws_slabs(Nb, C, Kout, nullptr, nullptr, nullptr);
+    auto ws = torch::empty({(long)SL * Kout * C * 9},
                            w.options().dtype(torch::kFloat));
     launch_conv_bwdw_tap_s2_bf16((const unsigned short*)dy.data_ptr(),
                                  (const unsigned short*)x.data_ptr(),
@@ -1462,6 +1464,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dropout_relu_bwd", &dropout_relu_bwd);
   m.def("batchnorm_bwd_into", &batchnorm_bwd_into);
   m.def("conv2d_bwd_wdx_into", &conv2d_bwd_wdx_into);
+  // (S, G, chunks, slabs): the tap bwd-weight launch plan and the
+  // workspace slabs bf16_dw allocates for it (host arithmetic only)
+  m.def("conv_bwdw_tap_ws_slabs", [](int64_t Nb, int64_t C, int64_t Kout) {
+    int S, G, chunks;
+    int slabs = conv_bwdw_tap_ws_slabs((int)Nb, (int)C, (int)Kout, &S, &G,
+                                       &chunks);
+    return std::make_tuple(S, G, chunks, slabs);
+  });
+  // the tap-family dispatch predicates, (C, H, W, Kout, R, S, stride,
+  // pad) in the argument order the call sites above use — exported so a
+  // test can pin which kernel a shape reaches
+  m.def("conv_tap_fwd_ok", [](int a, int b, int c, int d, int e, int f,
+                              int g, int h) {
+    return conv_tap_fwd_ok(a, b, c, d, e, f, g, h) != 0;
+  });
+  m.def("conv_tap_fwd_w4_ok", [](int a, int b, int c, int d, int e, int f,
+                                 int g, int h) {
+    return conv_tap_fwd_w4_ok(a, b, c, d, e, f, g, h) != 0;
+  });
+  m.def("conv_tap_bwdd_s2_ok", [](int a, int b, int c, int d, int e, int f,
+                                  int g, int h) {
+    return conv_tap_bwdd_s2_ok(a, b, c, d, e, f, g, h) != 0;
+  });
+  m.def("conv_bwdw_tap_ok", [](int a, int b, int c, int d, int e, int f,
+                               int g, int h) {
+    return conv_bwdw_tap_ok(a, b, c, d, e, f, g, h) != 0;
+  });
+  m.def("conv_bwdw_tap_s2_ok", [](int a, int b, int c, int d, int e, int f,
+                                  int g, int h) {
+    return conv_bwdw_tap_s2_ok(a, b, c, d, e, f, g, h) != 0;
+  });
   m.def("add_", &add_inplace);
   m.def("add_relu_bwd_", &add_relu_bwd_);
   m.def("gap_bwd_relu", &gap_bwd_relu);

@@ -254,14 +254,50 @@ int conv_bwdw_tap_slabs(int Nb, int C, int Kout) {
   return (int)s;
 }
 
+// The launch plan both tap bwd-weight launchers run AND the workspace
+// size bf16_dw allocates — one source of truth.  S image-group slabs of
+// G images each (G*S >= Nb); when S > 16 the two-stage combine writes
+// chunks = ceil(S/16) chunk sums into slabs S .. S+chunks-1 (chunks is 0
+// for the single-stage form).  Returns the slabs touched, S + chunks.
+int conv_bwdw_tap_ws_slabs(int Nb, int C, int Kout, int* S_out, int* G_out,
+                           int* chunks_out) {
+  int S = conv_bwdw_tap_slabs(Nb, C, Kout);
+  if (S < 1) S = 1;  // Nb == 0: one all-zero slab
+  int G = (Nb + S - 1) / S;
+  if (G < 1) G = 1;
+  S = (Nb + G - 1) / G;
+  if (S < 1) S = 1;
+  int chunks = S > 16 ? (S + 15) / 16 : 0;
+  if (S_out) *S_out = S;
+  if (G_out) *G_out = G;
+  if (chunks_out) *chunks_out = chunks;
+  return S + chunks;
+}
+
+// shared tail of both launchers: fold the S slabs into dw
+static void bwdw_tap_combine(float* ws, float* dw, long n_out, int S,
+                             int chunks, hipStream_t s) {
+  if (chunks > 0) {
+    // stage 1 writes its chunk sums PAST the S slabs (ws holds
+    // conv_bwdw_tap_ws_slabs slabs), then stage 2 folds the chunks
+    float* ws2 = ws + (long)S * n_out;
+    bwdw_tap_combine_k<<<grid_for(n_out * chunks), kBlock, 0, s>>>(
+        ws, ws2, n_out, S, 16);
+    bwdw_tap_combine_k<<<grid_for(n_out), kBlock, 0, s>>>(ws2, dw, n_out,
+                                                          chunks, chunks);
+  } else {
+    bwdw_tap_combine_k<<<grid_for(n_out), kBlock, 0, s>>>(ws, dw, n_out, S,
+                                                          S);
+  }
+}
+
 void launch_conv_bwdw_tap_bf16(const unsigned short* dy,
                                const unsigned short* x, float* dw,
                                float* ws, int Nb, int C, int H, int W,
                                int Kout, void* st) {
   hipStream_t s = (hipStream_t)st;
-  int S = conv_bwdw_tap_slabs(Nb, C, Kout);
-  int G = (Nb + S - 1) / S;
-  S = (Nb + G - 1) / G;
+  int S, G, chunks;
+  conv_bwdw_tap_ws_slabs(Nb, C, Kout, &S, &G, &chunks);
   if (W == 32) {
     dim3 grid(Kout / 32, C / 32, S);
     conv_bwdw_tap_bf16_k<5><<<grid, 256, 0, s>>>(dy, x, ws, Nb, C, H, Kout,
@@ -277,20 +313,7 @@ void launch_conv_bwdw_tap_bf16(const unsigned short* dy,
     conv_bwdw_tap_bf16_k<3><<<grid, 256, 0, s>>>(dy, x, ws, Nb, C, H, Kout,
                                                  G);
   }
-  long n_out = (long)Kout * C * 9;
-  if (S > 16) {
-    // stage 1 writes its chunk sums PAST the S slabs (ws is allocated
-    // with 16 extra slabs), then stage 2 folds the chunks
-    int chunks = (S + 15) / 16;
-    float* ws2 = ws + (long)S * n_out;
-    bwdw_tap_combine_k<<<grid_for(n_out * chunks), kBlock, 0, s>>>(
-        ws, ws2, n_out, S, 16);
-    bwdw_tap_combine_k<<<grid_for(n_out), kBlock, 0, s>>>(ws2, dw, n_out,
-                                                          chunks, chunks);
-  } else {
-    bwdw_tap_combine_k<<<grid_for(n_out), kBlock, 0, s>>>(ws, dw, n_out, S,
-                                                          S);
-  }
+  bwdw_tap_combine(ws, dw, (long)Kout * C * 9, S, chunks, s);
 }
 }
 
@@ -861,9 +884,8 @@ void launch_conv_bwdw_tap_s2_bf16(const unsigned short* dy,
                                   float* ws, int Nb, int C, int H, int W,
                                   int Kout, void* st) {
   hipStream_t s = (hipStream_t)st;
-  int S = conv_bwdw_tap_slabs(Nb, C, Kout);
-  int G = (Nb + S - 1) / S;
-  S = (Nb + G - 1) / G;
+  int S, G, chunks;
+  conv_bwdw_tap_ws_slabs(Nb, C, Kout, &S, &G, &chunks);
   dim3 grid(Kout / 32, C / 32, S);
   int OH = H / 2;
   if (W / 2 == 16)
@@ -872,18 +894,7 @@ void launch_conv_bwdw_tap_s2_bf16(const unsigned short* dy,
   else
     conv_bwdw_tap_s2_bf16_k<3><<<grid, 256, 0, s>>>(dy, x, ws, Nb, C, OH,
                                                     Kout, G);
-  long n_out = (long)Kout * C * 9;
-  if (S > 16) {
-    int chunks = (S + 15) / 16;
-    float* ws2 = ws + (long)S * n_out;
-    bwdw_tap_combine_k<<<grid_for(n_out * chunks), kBlock, 0, s>>>(
-        ws, ws2, n_out, S, 16);
-    bwdw_tap_combine_k<<<grid_for(n_out), kBlock, 0, s>>>(ws2, dw, n_out,
-                                                          chunks, chunks);
-  } else {
-    bwdw_tap_combine_k<<<grid_for(n_out), kBlock, 0, s>>>(ws, dw, n_out, S,
-                                                          S);
-  }
+  bwdw_tap_combine(ws, dw, (long)Kout * C * 9, S, chunks, s);
 }
 }
 
