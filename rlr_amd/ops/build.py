@@ -43,8 +43,8 @@ def _needs_rebuild(src, obj):
     mt = os.path.getmtime(obj)
     if os.path.getmtime(src) > mt:
         return True
-    hdr = os.path.join(CSRC, 'common.h')
-    return os.path.exists(hdr) and os.path.getmtime(hdr) > mt
+    return any(os.path.getmtime(os.path.join(CSRC, h)) > mt
+               for h in os.listdir(CSRC) if h.endswith('.h'))
 
 
 def _run(cmd):

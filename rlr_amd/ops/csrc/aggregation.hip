@@ -9,6 +9,7 @@
 // the fp32 parameter write — the matrix is read once instead of three
 // times (HBM-bound: K x n x 8 B per pass).
 #include "common.h"
+#include "launchers.h"
 
 // ---------------------------------------------------- fused avg+RLR+apply
 // mode_rlr: 0 = constant server_lr, 1 = RLR vote

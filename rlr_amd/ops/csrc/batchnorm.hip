@@ -12,6 +12,7 @@
 // each block idle and only 64 blocks on a 256-CU chip: 322 us for a 33 MB
 // pass that bn_norm_k covers in 8 us.
 #include "common.h"
+#include "launchers.h"
 
 constexpr int kBnChunksMax = 2048;  // partials allocation bound
 // row chunks scale with M: the big stem/L1 activations want deep stage-1

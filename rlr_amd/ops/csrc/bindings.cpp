@@ -1,10 +1,13 @@
 // Torch bindings for the rlr_amd HIP kernels.  This TU is the only one
 // that includes torch headers; the kernels are plain HIP compiled
-// separately (no hipify, no CUDA shims anywhere).
+// separately (no hipify, no CUDA shims anywhere).  The launchers and the
+// functions that size their workspaces are declared in launchers.h.
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
 #include <cstdint>
+
+#include "launchers.h"
 
 #define CHK(x) TORCH_CHECK(x, #x)
 #define CHK_CUDA(t)                                                      \
@@ -51,211 +54,17 @@ static torch::Tensor match_layout(const torch::Tensor& ref,
   return t.contiguous();
 }
 
-extern "C" {
-// elementwise.hip
-void launch_relu_fwd(const float*, float*, long, void*);
-void launch_relu_bwd(const float*, const float*, float*, long, void*);
-void launch_add_relu(const float*, const float*, float*, long, void*);
-void launch_add_inplace(float*, const float*, long, void*);
-void launch_add_inplace_bf16(unsigned short*, const unsigned short*, long,
-                             void*);
-void launch_maxpool2x2_fwd(const float*, float*, uint8_t*, long, int, int,
-                           int, int, int, void*);
-void launch_maxpool2x2_bwd(const float*, const uint8_t*, float*, long, int,
-                           int, int, int, int, void*);
-void launch_dropout_fwd(const float*, float*, uint8_t*, long, float,
-                        uint64_t, uint64_t, void*);
-void launch_dropout_fwd_dev(const float*, float*, uint8_t*, long, float,
-                            const unsigned long long*, int, void*);
-void launch_dropout_bwd(const float*, const uint8_t*, float*, long, float,
-                        void*);
-void launch_dropout_relu_bwd(const float*, const uint8_t*, const float*,
-                             float*, long, float, void*);
-void launch_maxpool2x2_bwd_relu(const float*, const uint8_t*, const float*,
-                                float*, long, int, int, int, int, int,
-                                void*);
-void launch_conv_bwd_data_relu(const float*, const float*, float*,
-                               const float*, int, int, int, int, int, int,
-                               int, int, int, int, int, void*);
-void launch_gap_fwd(const float*, float*, long, int, int, void*);
-void launch_gap_bwd(const float*, float*, long, int, int, void*);
-void launch_gap_bwd_relu(const float*, const float*, float*, long, int,
-                         int, void*);
-void launch_gap_bwd_relu_bf16(const unsigned short*, const unsigned short*,
-                              unsigned short*, long, int, int, void*);
-void launch_add_relu_bwd(float*, const float*, const float*, long, void*);
-void launch_add_relu_bwd_bf16(unsigned short*, const unsigned short*,
-                              const unsigned short*, long, void*);
-void launch_conv_bwd_data_bf16_relu(const unsigned short*,
-                                    const unsigned short*, unsigned short*,
-                                    const unsigned short*, int, int, int,
-                                    int, int, int, int, int, int, int, int,
-                                    void*);
-void launch_ce_fwd(const float*, const long*, float*, float*, float*, int,
-                   int, void*);
-void launch_ce_bwd(const float*, const long*, const float*, float*, int, int,
-                   void*);
-void launch_eval_update(const float*, const long*, float*, double*, int, int,
-                        int, void*);
-// flatopt.hip
-void launch_clipped_sgd(float*, const float*, float*, float*, float, float,
-                        float, long, void*);
-void launch_pgd_project(float*, const float*, float*, float, long, void*);
-void launch_delta64(const float*, const double*, double*, long, void*);
-void launch_gather_grads(const float* const*, const long*, const long*,
-                         int, float*, void*);
-// aggregation.hip
-void launch_fused_avg_rlr_apply(const double*, const double*, int, long,
-                                double, int, double, double, float*, double*,
-                                double, uint64_t, uint64_t, void*);
-void launch_rlr_vote(const double*, int, long, double, double, double*,
-                     void*);
-void launch_agg_avg(const double*, const double*, int, long, double, double*,
-                    void*);
-void launch_agg_sign(const double*, int, long, double*, void*);
-void launch_agg_comed(const double*, int, long, double*, void*);
-void launch_apply_update(float*, const double*, const double*, double, long,
-                         void*);
-void launch_add_noise(double*, double, long, uint64_t, uint64_t, void*);
-// orderstat.hip
-int orderstat_max_k();
-void launch_agg_orderstat(const double*, int, long, int, int, double, double*,
-                          double*, double, double, void*);
-void launch_orderstat_rlr_apply(const double*, int, long, int, int, double,
-                                int, double, double, float*, double*, void*);
-// gemm_f32.hip
-int gemm_f32_splitk(int, int, int);
-void launch_gemm_f32(const float*, const float*, float*, const float*,
-                     float*, int, int, int, int, int, int, int, int, int,
-                     void*);
-void launch_colsum(const float*, float*, int, int, void*);
-// conv_f32.hip
-void launch_conv_fwd(const float*, const float*, const float*, float*, int,
-                     int, int, int, int, int, int, int, int, int, int, int,
-                     void*);
-void launch_conv_bwd_data(const float*, const float*, float*, int, int, int,
-                          int, int, int, int, int, int, int, int, void*);
-int conv_bwd_weight_splitk(int, int, long);
-int conv_bwd_weight_bf16_splitk(int, int, long);
-void launch_conv_bwd_weight(const float*, const float*, float*, float*, int,
-                            int, int, int, int, int, int, int, int, int, int,
-                            int, void*);
-void launch_conv_db(const float*, float*, float*, int, int, int, void*);
-void launch_wperm_crs_ko(const float*, float*, int, int, int, void*);
-void launch_wperm_kors_c(const float*, float*, int, int, int, void*);
-// gemm_bf16.hip
-void launch_gemm_bf16(const unsigned short*, const unsigned short*, float*,
-                      const float*, unsigned short*, float*, int, int, int,
-                      int, int, int, int, int, void*);
-void launch_f32_to_bf16(const float*, unsigned short*, long, void*);
-void launch_bf16_to_f32(const unsigned short*, float*, long, void*);
-// conv_bf16.hip
-void launch_conv_fwd_bf16(const unsigned short*, const unsigned short*,
-                          const float*, unsigned short*, int, int, int, int,
-                          int, int, int, int, int, int, int, int, void*);
-void launch_conv_bwd_data_bf16(const unsigned short*, const unsigned short*,
-                               unsigned short*, int, int, int, int, int,
-                               int, int, int, int, int, int, void*);
-void launch_conv_bwd_weight_bf16(const unsigned short*,
-                                 const unsigned short*, float*, float*, int,
-                                 int, int, int, int, int, int, int, int,
-                                 int, int, int, void*);
-// conv_bwdw_tap.hip
-int conv_bwdw_tap_ok(int, int, int, int, int, int, int, int);
-int conv_bwdw_tap_s2_ok(int, int, int, int, int, int, int, int);
-int conv_bwdw_tap_slabs(int, int, int);
-int conv_bwdw_tap_ws_slabs(int, int, int, int*, int*, int*);
-void launch_conv_bwdw_tap_s2_bf16(const unsigned short*,
-                                  const unsigned short*, float*, float*,
-                                  int, int, int, int, int, void*);
-void launch_conv_bwdw_tap_bf16(const unsigned short*, const unsigned short*,
-                               float*, float*, int, int, int, int, int,
-                               void*);
-int conv_tap_fwd_ok(int, int, int, int, int, int, int, int);
-void launch_conv_tap_fwd_bf16(const unsigned short*, const unsigned short*,
-                              const float*, unsigned short*,
-                              const unsigned short*, int, int, int, int,
-                              int, int, int, void*);
-int conv_tap_bwdd_s2_ok(int, int, int, int, int, int, int, int);
-int conv_tap_fwd_w4_ok(int, int, int, int, int, int, int, int);
-void launch_conv_tap_fwd_w4_bf16(const unsigned short*,
-                                 const unsigned short*, const float*,
-                                 unsigned short*, const unsigned short*,
-                                 int, int, int, int, int, void*);
-void launch_conv_tap_bwdd_s2_bf16(const unsigned short*,
-                                  const unsigned short*, unsigned short*,
-                                  const unsigned short*, int, int, int,
-                                  int, int, void*);
-void launch_wperm_rsc_ko_bf16(const float*, unsigned short*, int, int, int,
-                              void*);
-void launch_wperm_rsko_c_bf16(const float*, unsigned short*, int, int, int,
-                              void*);
-void launch_conv_db_bf16(const unsigned short*, float*, float*, int, int,
-                         int, void*);
-// elementwise bf16
-void launch_relu_fwd_bf16(const unsigned short*, unsigned short*, long,
-                          void*);
-void launch_relu_bwd_bf16(const unsigned short*, const unsigned short*,
-                          unsigned short*, long, void*);
-void launch_add_relu_bf16(const unsigned short*, const unsigned short*,
-                          unsigned short*, long, void*);
-void launch_dropout_fwd_dev_bf16(const unsigned short*, unsigned short*,
-                                 uint8_t*, long, float,
-                                 const unsigned long long*, int, void*);
-void launch_dropout_bwd_bf16(const unsigned short*, const uint8_t*,
-                             unsigned short*, long, float, void*);
-void launch_gap_fwd_bf16(const unsigned short*, unsigned short*, long, int,
-                         int, void*);
-void launch_gap_bwd_bf16(const unsigned short*, unsigned short*, long, int,
-                         int, void*);
-void launch_maxpool2x2_fwd_bf16(const unsigned short*, unsigned short*,
-                                uint8_t*, long, int, int, int, int, int,
-                                void*);
-void launch_maxpool2x2_bwd_bf16(const unsigned short*, const uint8_t*,
-                                unsigned short*, long, int, int, int, int,
-                                int, void*);
-// flatten
-void launch_nhwc_flatten(const float*, float*, long, int, int, int, void*);
-void launch_nhwc_unflatten(const float*, float*, long, int, int, int,
-                           void*);
-void launch_nhwc_flatten_bf16(const unsigned short*, unsigned short*, long,
-                              int, int, int, void*);
-void launch_nhwc_unflatten_bf16(const unsigned short*, unsigned short*,
-                                long, int, int, int, void*);
-// batchnorm bf16
-void launch_bn_fwd_bf16(const unsigned short*, const float*, const float*,
-                        float*, float*, float*, float*, unsigned short*,
-                        float*, int, int, int, float, float, int, int,
-                        void*);
-void launch_bn_bwd_bf16(const unsigned short*, const unsigned short*,
-                        const float*, const float*, const float*, float*,
-                        unsigned short*, float*, float*, int, int, int, int,
-                        void*);
-// batchnorm.hip
-int bn_scratch_floats(int);
-void launch_bn_fwd(const float*, const float*, const float*, float*, float*,
-                   float*, float*, float*, float*, int, int, int, float,
-                   float, int, int, void*);
-void launch_bn_bwd(const float*, const float*, const float*, const float*,
-                   const float*, float*, float*, float*, float*, int, int,
-                   int, int, void*);
-// poison.hip
-void launch_poison_set_u8(uint8_t*, const long*, int, const int*, int, int,
-                          int, int, int, void*);
-void launch_poison_set_f32(float*, const long*, int, const int*, int, int,
-                           int, float, void*);
-void launch_poison_addwrap_u8(uint8_t*, const long*, int, const uint8_t*,
-                              int, void*);
-void launch_poison_subf(float*, const long*, int, const uint8_t*, int,
-                        void*);
-void launch_normalize_u8(const uint8_t*, float*, long, int, int, int,
-                         const float*, const float*, void*);
-}
-
 namespace {
 
 static bool is_bf16(const torch::Tensor& t) {
   return t.scalar_type() == torch::kBFloat16;
+}
+// bf16 storage as the launchers take it (raw ushort): read / write side
+static const unsigned short* bfc(const torch::Tensor& t) {
+  return (const unsigned short*)t.data_ptr();
+}
+static unsigned short* bfp(const torch::Tensor& t) {
+  return (unsigned short*)t.data_ptr();
 }
 
 
@@ -264,14 +73,11 @@ static bool is_bf16(const torch::Tensor& t) {
 torch::Tensor relu_fwd(torch::Tensor x) {
   CHK_CUDA(x);
   auto y = torch::empty_like(x);
-  if (is_bf16(x)) {
-    launch_relu_fwd_bf16((const unsigned short*)x.data_ptr(),
-                         (unsigned short*)y.data_ptr(), x.numel(),
-                         stream_of(x));
-    return y;
-  }
-  launch_relu_fwd(x.data_ptr<float>(), y.data_ptr<float>(), x.numel(),
-                  stream_of(x));
+  if (is_bf16(x))
+    launch_relu_fwd_bf16(bfc(x), bfp(y), x.numel(), stream_of(x));
+  else
+    launch_relu_fwd(x.data_ptr<float>(), y.data_ptr<float>(), x.numel(),
+                    stream_of(x));
   return y;
 }
 
@@ -279,15 +85,11 @@ torch::Tensor relu_bwd(torch::Tensor y, torch::Tensor dy) {
   CHK_CUDA(y);
   dy = match_layout(y, dy);
   auto dx = torch::empty_like(y);
-  if (is_bf16(y)) {
-    launch_relu_bwd_bf16((const unsigned short*)y.data_ptr(),
-                         (const unsigned short*)dy.data_ptr(),
-                         (unsigned short*)dx.data_ptr(), y.numel(),
-                         stream_of(y));
-    return dx;
-  }
-  launch_relu_bwd(y.data_ptr<float>(), dy.data_ptr<float>(),
-                  dx.data_ptr<float>(), y.numel(), stream_of(y));
+  if (is_bf16(y))
+    launch_relu_bwd_bf16(bfc(y), bfc(dy), bfp(dx), y.numel(), stream_of(y));
+  else
+    launch_relu_bwd(y.data_ptr<float>(), dy.data_ptr<float>(),
+                    dx.data_ptr<float>(), y.numel(), stream_of(y));
   return dx;
 }
 
@@ -295,15 +97,11 @@ torch::Tensor add_relu_fwd(torch::Tensor a, torch::Tensor b) {
   CHK_CUDA(a);
   b = match_layout(a, b);
   auto y = torch::empty_like(a);
-  if (is_bf16(a)) {
-    launch_add_relu_bf16((const unsigned short*)a.data_ptr(),
-                         (const unsigned short*)b.data_ptr(),
-                         (unsigned short*)y.data_ptr(), a.numel(),
-                         stream_of(a));
-    return y;
-  }
-  launch_add_relu(a.data_ptr<float>(), b.data_ptr<float>(),
-                  y.data_ptr<float>(), a.numel(), stream_of(a));
+  if (is_bf16(a))
+    launch_add_relu_bf16(bfc(a), bfc(b), bfp(y), a.numel(), stream_of(a));
+  else
+    launch_add_relu(a.data_ptr<float>(), b.data_ptr<float>(),
+                    y.data_ptr<float>(), a.numel(), stream_of(a));
   return y;
 }
 
@@ -315,10 +113,8 @@ std::tuple<torch::Tensor, torch::Tensor> maxpool2x2_fwd(torch::Tensor x) {
   auto y = empty_cl({Nb, C, OH, OW}, x.options());
   auto idx = empty_cl({Nb, C, OH, OW}, x.options().dtype(torch::kUInt8));
   if (is_bf16(x))
-    launch_maxpool2x2_fwd_bf16((const unsigned short*)x.data_ptr(),
-                               (unsigned short*)y.data_ptr(),
-                               idx.data_ptr<uint8_t>(), Nb, H, W, OH, OW, C,
-                               stream_of(x));
+    launch_maxpool2x2_fwd_bf16(bfc(x), bfp(y), idx.data_ptr<uint8_t>(), Nb,
+                               H, W, OH, OW, C, stream_of(x));
   else
     launch_maxpool2x2_fwd(x.data_ptr<float>(), y.data_ptr<float>(),
                           idx.data_ptr<uint8_t>(), Nb, H, W, OH, OW, C,
@@ -334,10 +130,8 @@ torch::Tensor maxpool2x2_bwd(torch::Tensor dy, torch::Tensor idx,
   int OH = dy.size(2), OW = dy.size(3);
   auto dx = empty_cl({Nb, C, H, W}, dy.options());
   if (is_bf16(dy))
-    launch_maxpool2x2_bwd_bf16((const unsigned short*)dy.data_ptr(),
-                               idx.data_ptr<uint8_t>(),
-                               (unsigned short*)dx.data_ptr(), Nb, H, W, OH,
-                               OW, C, stream_of(dy));
+    launch_maxpool2x2_bwd_bf16(bfc(dy), idx.data_ptr<uint8_t>(), bfp(dx),
+                               Nb, H, W, OH, OW, C, stream_of(dy));
   else
     launch_maxpool2x2_bwd(dy.data_ptr<float>(), idx.data_ptr<uint8_t>(),
                           dx.data_ptr<float>(), Nb, H, W, OH, OW, C,
@@ -352,10 +146,8 @@ torch::Tensor add_relu_bwd_(torch::Tensor a, torch::Tensor b,
   CHK_CUDA(a);
   TORCH_CHECK(a.numel() == b.numel() && a.numel() == relu_y.numel());
   if (is_bf16(a))
-    launch_add_relu_bwd_bf16((unsigned short*)a.data_ptr(),
-                             (const unsigned short*)b.data_ptr(),
-                             (const unsigned short*)relu_y.data_ptr(),
-                             a.numel(), stream_of(a));
+    launch_add_relu_bwd_bf16(bfp(a), bfc(b), bfc(relu_y), a.numel(),
+                             stream_of(a));
   else
     launch_add_relu_bwd(a.data_ptr<float>(), b.data_ptr<float>(),
                         relu_y.data_ptr<float>(), a.numel(), stream_of(a));
@@ -371,9 +163,7 @@ torch::Tensor gap_bwd_relu(torch::Tensor dy, torch::Tensor relu_y,
   auto dx = empty_cl(in_shape, relu_y.options());
   relu_y = cl(relu_y, "gap_bwd.relu");
   if (is_bf16(relu_y))
-    launch_gap_bwd_relu_bf16((const unsigned short*)dy.data_ptr(),
-                             (const unsigned short*)relu_y.data_ptr(),
-                             (unsigned short*)dx.data_ptr(), Nb, HW, C,
+    launch_gap_bwd_relu_bf16(bfc(dy), bfc(relu_y), bfp(dx), Nb, HW, C,
                              stream_of(dy));
   else
     launch_gap_bwd_relu(dy.data_ptr<float>(), relu_y.data_ptr<float>(),
@@ -386,9 +176,7 @@ torch::Tensor add_inplace(torch::Tensor a, torch::Tensor b) {
   CHK_CUDA(a);
   TORCH_CHECK(a.numel() == b.numel() && a.scalar_type() == b.scalar_type());
   if (is_bf16(a))
-    launch_add_inplace_bf16((unsigned short*)a.data_ptr(),
-                            (const unsigned short*)b.data_ptr(), a.numel(),
-                            stream_of(a));
+    launch_add_inplace_bf16(bfp(a), bfc(b), a.numel(), stream_of(a));
   else
     launch_add_inplace(a.data_ptr<float>(), b.data_ptr<float>(), a.numel(),
                        stream_of(a));
@@ -436,8 +224,7 @@ std::tuple<torch::Tensor, torch::Tensor> dropout_fwd_dev(torch::Tensor x,
   auto mask = torch::empty(x.sizes(), x.options().dtype(torch::kUInt8));
   if (is_bf16(x))
     launch_dropout_fwd_dev_bf16(
-        (const unsigned short*)x.data_ptr(), (unsigned short*)y.data_ptr(),
-        mask.data_ptr<uint8_t>(), x.numel(), (float)p,
+        bfc(x), bfp(y), mask.data_ptr<uint8_t>(), x.numel(), (float)p,
         (const unsigned long long*)state.data_ptr(), (int)site,
         stream_of(x));
   else
@@ -453,10 +240,8 @@ torch::Tensor dropout_bwd(torch::Tensor dy, torch::Tensor mask, double p) {
   CHK_CUDA(dy);
   auto dx = torch::empty_like(dy);
   if (is_bf16(dy))
-    launch_dropout_bwd_bf16((const unsigned short*)dy.data_ptr(),
-                            mask.data_ptr<uint8_t>(),
-                            (unsigned short*)dx.data_ptr(), dy.numel(),
-                            (float)p, stream_of(dy));
+    launch_dropout_bwd_bf16(bfc(dy), mask.data_ptr<uint8_t>(), bfp(dx),
+                            dy.numel(), (float)p, stream_of(dy));
   else
     launch_dropout_bwd(dy.data_ptr<float>(), mask.data_ptr<uint8_t>(),
                        dx.data_ptr<float>(), dy.numel(), (float)p,
@@ -483,9 +268,7 @@ torch::Tensor gap_fwd(torch::Tensor x) {
   int Nb = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
   auto y = torch::empty({Nb, C}, x.options());
   if (is_bf16(x))
-    launch_gap_fwd_bf16((const unsigned short*)x.data_ptr(),
-                        (unsigned short*)y.data_ptr(), Nb, HW, C,
-                        stream_of(x));
+    launch_gap_fwd_bf16(bfc(x), bfp(y), Nb, HW, C, stream_of(x));
   else
     launch_gap_fwd(x.data_ptr<float>(), y.data_ptr<float>(), Nb, HW, C,
                    stream_of(x));
@@ -498,9 +281,7 @@ torch::Tensor gap_bwd(torch::Tensor dy, std::vector<int64_t> in_shape) {
   int Nb = in_shape[0], C = in_shape[1], HW = in_shape[2] * in_shape[3];
   auto dx = empty_cl({Nb, C, in_shape[2], in_shape[3]}, dy.options());
   if (is_bf16(dy))
-    launch_gap_bwd_bf16((const unsigned short*)dy.data_ptr(),
-                        (unsigned short*)dx.data_ptr(), Nb, HW, C,
-                        stream_of(dy));
+    launch_gap_bwd_bf16(bfc(dy), bfp(dx), Nb, HW, C, stream_of(dy));
   else
     launch_gap_bwd(dy.data_ptr<float>(), dx.data_ptr<float>(), Nb, HW, C,
                    stream_of(dy));
@@ -552,9 +333,7 @@ torch::Tensor nhwc_flatten(torch::Tensor x) {
   int C = x.size(1), H = x.size(2), W = x.size(3);
   auto out = torch::empty({B, (long)C * H * W}, x.options());
   if (is_bf16(x))
-    launch_nhwc_flatten_bf16((const unsigned short*)x.data_ptr(),
-                             (unsigned short*)out.data_ptr(), B, C, H, W,
-                             stream_of(x));
+    launch_nhwc_flatten_bf16(bfc(x), bfp(out), B, C, H, W, stream_of(x));
   else
     launch_nhwc_flatten(x.data_ptr<float>(), out.data_ptr<float>(), B, C,
                         H, W, stream_of(x));
@@ -568,9 +347,8 @@ torch::Tensor nhwc_unflatten(torch::Tensor g, int64_t C, int64_t H,
   long B = g.size(0);
   auto out = empty_cl({B, C, H, W}, g.options());
   if (is_bf16(g))
-    launch_nhwc_unflatten_bf16((const unsigned short*)g.data_ptr(),
-                               (unsigned short*)out.data_ptr(), B, (int)C,
-                               (int)H, (int)W, stream_of(g));
+    launch_nhwc_unflatten_bf16(bfc(g), bfp(out), B, (int)C, (int)H, (int)W,
+                               stream_of(g));
   else
     launch_nhwc_unflatten(g.data_ptr<float>(), out.data_ptr<float>(), B,
                           (int)C, (int)H, (int)W, stream_of(g));
@@ -582,7 +360,7 @@ torch::Tensor nhwc_unflatten(torch::Tensor g, int64_t C, int64_t H,
 void clipped_sgd_step(torch::Tensor p, torch::Tensor g, torch::Tensor v,
                       double lr, double mu, double max_norm) {
   CHK_CUDA(p);
-  auto scratch = torch::empty({1025}, p.options());
+  auto scratch = torch::empty({flat_norm_scratch_floats()}, p.options());
   launch_clipped_sgd(p.data_ptr<float>(), g.data_ptr<float>(),
                      v.data_ptr<float>(), scratch.data_ptr<float>(),
                      (float)lr, (float)mu, (float)max_norm, p.numel(),
@@ -591,7 +369,7 @@ void clipped_sgd_step(torch::Tensor p, torch::Tensor g, torch::Tensor v,
 
 void pgd_project(torch::Tensor p, torch::Tensor t0, double clip) {
   CHK_CUDA(p);
-  auto scratch = torch::empty({1025}, p.options());
+  auto scratch = torch::empty({flat_norm_scratch_floats()}, p.options());
   launch_pgd_project(p.data_ptr<float>(), t0.data_ptr<float>(),
                      scratch.data_ptr<float>(), (float)clip, p.numel(),
                      stream_of(p));
@@ -636,6 +414,12 @@ torch::Tensor delta64(torch::Tensor p, torch::Tensor t0) {
 
 // ------------------------------------------------------------ aggregation
 
+// the per-coordinate learning-rate output: n doubles, or empty (and a null
+// pointer to the launcher) when the caller does not want it
+static torch::Tensor lr_buf(bool want_lr, long n, const torch::Tensor& U) {
+  return torch::empty({want_lr ? n : 0}, U.options());
+}
+
 torch::Tensor fused_avg_rlr_apply(torch::Tensor U, torch::Tensor w,
                                   torch::Tensor params, bool rlr,
                                   double thresh, double slr,
@@ -646,8 +430,7 @@ torch::Tensor fused_avg_rlr_apply(torch::Tensor U, torch::Tensor w,
   int K = U.size(0);
   long n = U.size(1);
   double wsum = w.sum().item<double>();
-  auto lr = want_lr ? torch::empty({n}, U.options())
-                    : torch::empty({0}, U.options());
+  auto lr = lr_buf(want_lr, n, U);
   launch_fused_avg_rlr_apply(
       U.data_ptr<double>(), w.data_ptr<double>(), K, n, 1.0 / wsum,
       rlr ? 1 : 0, thresh, slr, params.data_ptr<float>(),
@@ -713,8 +496,7 @@ std::tuple<torch::Tensor, torch::Tensor> agg_orderstat(
   int K = U.size(0);
   long n = U.size(1);
   auto out = torch::empty({n}, U.options());
-  auto lr = want_lr ? torch::empty({n}, U.options())
-                    : torch::empty({0}, U.options());
+  auto lr = lr_buf(want_lr, n, U);
   launch_agg_orderstat(U.data_ptr<double>(), K, n, (int)lo, (int)hi,
                        1.0 / (double)(hi - lo), out.data_ptr<double>(),
                        want_lr ? lr.data_ptr<double>() : nullptr, thresh, slr,
@@ -732,8 +514,7 @@ torch::Tensor orderstat_rlr_apply(torch::Tensor U, int64_t lo, int64_t hi,
   CHK(params.numel() == U.size(1));
   int K = U.size(0);
   long n = U.size(1);
-  auto lr = want_lr ? torch::empty({n}, U.options())
-                    : torch::empty({0}, U.options());
+  auto lr = lr_buf(want_lr, n, U);
   launch_orderstat_rlr_apply(U.data_ptr<double>(), K, n, (int)lo, (int)hi,
                              1.0 / (double)(hi - lo), rlr ? 1 : 0, thresh,
                              slr, params.data_ptr<float>(),
@@ -758,48 +539,34 @@ void add_noise(torch::Tensor agg, double std, int64_t seed, int64_t offset) {
 
 // ------------------------------------------------------------ gemm/linear
 
+// The fp32 GEMM driver with explicit operand layout: C (M,N) = op(A)
+// op(B) (+bias, relu).  C is the caller-owned contiguous output when
+// given (manual tape: a flat-grad view), freshly allocated otherwise.
+static torch::Tensor gemm_f32(const torch::Tensor& A, const torch::Tensor& B,
+                              c10::optional<torch::Tensor> bias, bool relu,
+                              int M, int N, int K, int lda, int ldb,
+                              int layout,
+                              torch::Tensor C = torch::Tensor()) {
+  if (!C.defined()) C = torch::empty({M, N}, A.options());
+  int SK = gemm_f32_splitk(M, N, K);
+  torch::Tensor ws;  // split-K slabs; none for SK == 1
+  if (SK > 1)
+    ws = torch::empty({gemm_splitk_ws_floats(M, N, SK)}, A.options());
+  launch_gemm_f32(A.data_ptr<float>(), B.data_ptr<float>(),
+                  C.data_ptr<float>(),
+                  bias ? bias->data_ptr<float>() : nullptr,
+                  SK > 1 ? ws.data_ptr<float>() : nullptr, M, N, K, lda, ldb,
+                  N, SK, relu ? 1 : 0, layout, stream_of(A));
+  return C;
+}
+
 torch::Tensor gemm(torch::Tensor A, torch::Tensor B,
                    c10::optional<torch::Tensor> bias, bool relu) {
   CHK_CUDA(A);
   CHK_CUDA(B);
   int M = A.size(0), K = A.size(1), N = B.size(1);
   CHK(B.size(0) == K);
-  auto C = torch::empty({M, N}, A.options());
-  int SK = gemm_f32_splitk(M, N, K);
-  torch::Tensor ws;
-  float* wsp = nullptr;
-  if (SK > 1) {
-    ws = torch::empty({((long)SK + (SK > 16 ? (SK + 15) / 16 : 0)) * M *
-                       N}, A.options());
-    wsp = ws.data_ptr<float>();
-  }
-  launch_gemm_f32(A.data_ptr<float>(), B.data_ptr<float>(),
-                  C.data_ptr<float>(),
-                  bias ? bias->data_ptr<float>() : nullptr, wsp, M, N, K, K,
-                  N, N, SK, relu ? 1 : 0, 0, stream_of(A));
-  return C;
-}
-
-// shared fp32 GEMM driver with explicit operand layout
-static torch::Tensor gemm_layout(const torch::Tensor& A,
-                                 const torch::Tensor& B,
-                                 c10::optional<torch::Tensor> bias,
-                                 bool relu, int M, int N, int K, int lda,
-                                 int ldb, int layout) {
-  auto C = torch::empty({M, N}, A.options());
-  int SK = gemm_f32_splitk(M, N, K);
-  torch::Tensor ws;
-  float* wsp = nullptr;
-  if (SK > 1) {
-    ws = torch::empty({((long)SK + (SK > 16 ? (SK + 15) / 16 : 0)) * M *
-                       N}, A.options());
-    wsp = ws.data_ptr<float>();
-  }
-  launch_gemm_f32(A.data_ptr<float>(), B.data_ptr<float>(),
-                  C.data_ptr<float>(),
-                  bias ? bias->data_ptr<float>() : nullptr, wsp, M, N, K,
-                  lda, ldb, N, SK, relu ? 1 : 0, layout, stream_of(A));
-  return C;
+  return gemm_f32(A, B, bias, relu, M, N, K, K, N, 0);
 }
 
 // bf16 GEMM: A (M,K) bf16, B (K,N) bf16 -> C fp32 (or bf16 if out_bf16)
@@ -815,24 +582,19 @@ torch::Tensor gemm_bf16(torch::Tensor A, torch::Tensor B,
   torch::Tensor ws;
   float* wsp = nullptr;
   if (SK > 1) {
-    ws = torch::empty({((long)SK + (SK > 16 ? (SK + 15) / 16 : 0)) * M *
-                       N}, A.options().dtype(torch::kFloat));
+    ws = torch::empty({gemm_splitk_ws_floats(M, N, SK)},
+                      A.options().dtype(torch::kFloat));
     wsp = ws.data_ptr<float>();
   }
+  const float* bp = bias ? bias->data_ptr<float>() : nullptr;
   torch::Tensor C;
   if (out_bf16 && SK == 1) {
     C = torch::empty({M, N}, A.options());
-    launch_gemm_bf16((const unsigned short*)A.data_ptr(),
-                     (const unsigned short*)B.data_ptr(), nullptr,
-                     bias ? bias->data_ptr<float>() : nullptr,
-                     (unsigned short*)C.data_ptr(), wsp, M, N, K, K, N, N,
-                     SK, relu ? 1 : 0, stream_of(A));
+    launch_gemm_bf16(bfc(A), bfc(B), nullptr, bp, bfp(C), wsp, M, N, K, K,
+                     N, N, SK, relu ? 1 : 0, stream_of(A));
   } else {
     C = torch::empty({M, N}, A.options().dtype(torch::kFloat));
-    launch_gemm_bf16((const unsigned short*)A.data_ptr(),
-                     (const unsigned short*)B.data_ptr(),
-                     C.data_ptr<float>(),
-                     bias ? bias->data_ptr<float>() : nullptr, nullptr, wsp,
+    launch_gemm_bf16(bfc(A), bfc(B), C.data_ptr<float>(), bp, nullptr, wsp,
                      M, N, K, K, N, N, SK, relu ? 1 : 0, stream_of(A));
     if (out_bf16) C = C.to(torch::kBFloat16);
   }
@@ -851,35 +613,13 @@ torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w,
   x = x.contiguous();
   w = w.contiguous();
   int M = x.size(0), K = x.size(1), N = w.size(0);
-  return gemm_layout(x, w, b, relu, M, N, K, K, K, 2);
+  return gemm_f32(x, w, b, relu, M, N, K, K, K, 2);
 }
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> linear_bwd(
-    torch::Tensor x, torch::Tensor w, torch::Tensor dy) {
-  dy = dy.contiguous();
-  if (is_bf16(x)) {
-    auto w16 = w.to(torch::kBFloat16).contiguous();
-    auto dx = gemm_bf16(dy, w16, c10::nullopt, false, /*out_bf16=*/true);
-    auto dyt = dy.t().contiguous();
-    auto dw = gemm_bf16(dyt, x.contiguous(), c10::nullopt, false, false);
-    auto db = dy.to(torch::kFloat).sum(0);
-    return {dx, dw, db};
-  }
-  x = x.contiguous();
-  w = w.contiguous();
-  int bM = x.size(0), in = x.size(1), out = w.size(0);
-  // dx = dY (M,out) @ W (out,in): plain NN
-  auto dx = gemm_layout(dy, w, c10::nullopt, false, bM, in, out, out, in, 0);
-  // dw = dY^T @ X: A = dY consumed transposed (layout 1)
-  auto dw = gemm_layout(dy, x, c10::nullopt, false, out, in, bM, out, in, 1);
-  auto db = torch::empty({out}, dy.options());
-  launch_colsum(dy.data_ptr<float>(), db.data_ptr<float>(), bM, out,
-                stream_of(dy));
-  return {dx, dw, db};
-}
-
-// manual-tape variant: dw/db written into caller-owned views (see
-// conv2d_bwd_into below for the rationale); fp32 only.
+// manual-tape variant, fp32 only: dw/db written into caller-owned views
+// (see conv2d_bwd_into below for the rationale).  dx = dY (M,out) @ W
+// (out,in): plain NN, skipped (undefined) unless need_dx; dw = dY^T @ X:
+// A = dY consumed transposed (layout 1); db = column sums of dY.
 torch::Tensor linear_bwd_into(torch::Tensor x, torch::Tensor w,
                               torch::Tensor dy, torch::Tensor dw_out,
                               c10::optional<torch::Tensor> db_out,
@@ -889,24 +629,11 @@ torch::Tensor linear_bwd_into(torch::Tensor x, torch::Tensor w,
   x = x.contiguous();
   w = w.contiguous();
   int bM = x.size(0), in = x.size(1), out = w.size(0);
-  TORCH_CHECK(dw_out.is_contiguous() &&
-              dw_out.numel() == (long)out * in);
+  TORCH_CHECK(dw_out.is_contiguous() && dw_out.numel() == (long)out * in);
   torch::Tensor dx;
   if (need_dx)
-    dx = gemm_layout(dy, w, c10::nullopt, false, bM, in, out, out, in, 0);
-  {  // dw = dY^T @ X straight into the view
-    int SK = gemm_f32_splitk(out, in, bM);
-    torch::Tensor ws;
-    float* wsp = nullptr;
-    if (SK > 1) {
-      ws = torch::empty({((long)SK + (SK > 16 ? (SK + 15) / 16 : 0)) *
-                         out * in}, x.options());
-      wsp = ws.data_ptr<float>();
-    }
-    launch_gemm_f32(dy.data_ptr<float>(), x.data_ptr<float>(),
-                    dw_out.data_ptr<float>(), nullptr, wsp, out, in, bM,
-                    out, in, in, SK, 0, 1, stream_of(dy));
-  }
+    dx = gemm_f32(dy, w, c10::nullopt, false, bM, in, out, out, in, 0);
+  gemm_f32(dy, x, c10::nullopt, false, out, in, bM, out, in, 1, dw_out);
   if (db_out) {
     TORCH_CHECK(db_out->is_contiguous() && db_out->numel() == out);
     launch_colsum(dy.data_ptr<float>(), db_out->data_ptr<float>(), bM, out,
@@ -915,11 +642,25 @@ torch::Tensor linear_bwd_into(torch::Tensor x, torch::Tensor w,
   return dx;
 }
 
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> linear_bwd(
+    torch::Tensor x, torch::Tensor w, torch::Tensor dy) {
+  if (is_bf16(x)) {
+    dy = dy.contiguous();
+    auto w16 = w.to(torch::kBFloat16).contiguous();
+    auto dx = gemm_bf16(dy, w16, c10::nullopt, false, /*out_bf16=*/true);
+    auto dyt = dy.t().contiguous();
+    auto dw = gemm_bf16(dyt, x.contiguous(), c10::nullopt, false, false);
+    auto db = dy.to(torch::kFloat).sum(0);
+    return {dx, dw, db};
+  }
+  auto dw = torch::empty({w.size(0), w.size(1)}, dy.options());
+  auto db = torch::empty({w.size(0)}, dy.options());
+  auto dx = linear_bwd_into(x, w, dy, dw, db, true);
+  return {dx, dw, db};
+}
+
 // ------------------------------------------------------------------ conv
 
-torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w,
-                         c10::optional<torch::Tensor> b, int64_t stride,
-                         int64_t pad, bool relu);
 torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w,
                          c10::optional<torch::Tensor> b, int64_t stride,
                          int64_t pad, bool relu) {
@@ -930,34 +671,25 @@ torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w,
   int Kout = w.size(0), R = w.size(2), S = w.size(3);
   int OH = (H + 2 * pad - R) / stride + 1;
   int OW = (W + 2 * pad - S) / stride + 1;
+  const float* bp = b ? b->data_ptr<float>() : nullptr;
   if (is_bf16(x)) {
     if ((C % 32) == 0) {
       auto wt = torch::empty({(long)C * R * S, Kout},
                              w.options().dtype(torch::kBFloat16));
-      launch_wperm_rsc_ko_bf16(w.data_ptr<float>(),
-                               (unsigned short*)wt.data_ptr(), Kout, C,
-                               R * S, stream_of(x));
+      launch_wperm_rsc_ko_bf16(w.data_ptr<float>(), bfp(wt), Kout, C, R * S,
+                               stream_of(x));
       auto y = empty_cl({Nb, Kout, OH, OW}, x.options());
       if (conv_tap_fwd_w4_ok(C, H, W, Kout, R, S, (int)stride, (int)pad))
-        launch_conv_tap_fwd_w4_bf16(
-            (const unsigned short*)x.data_ptr(),
-            (const unsigned short*)wt.data_ptr(),
-            b ? b->data_ptr<float>() : nullptr,
-            (unsigned short*)y.data_ptr(), nullptr, Nb, C, Kout,
-            relu ? 1 : 0, 0, stream_of(x));
+        launch_conv_tap_fwd_w4_bf16(bfc(x), bfc(wt), bp, bfp(y),
+                                    nullptr, Nb, C, Kout, relu ? 1 : 0, 0,
+                                    stream_of(x));
       else if (conv_tap_fwd_ok(C, H, W, Kout, R, S, (int)stride, (int)pad))
-        launch_conv_tap_fwd_bf16((const unsigned short*)x.data_ptr(),
-                                 (const unsigned short*)wt.data_ptr(),
-                                 b ? b->data_ptr<float>() : nullptr,
-                                 (unsigned short*)y.data_ptr(), nullptr,
-                                 Nb, C, H, W, Kout, relu ? 1 : 0, 0,
+        launch_conv_tap_fwd_bf16(bfc(x), bfc(wt), bp, bfp(y),
+                                 nullptr, Nb, C, H, W, Kout, relu ? 1 : 0, 0,
                                  stream_of(x));
       else
-        launch_conv_fwd_bf16((const unsigned short*)x.data_ptr(),
-                             (const unsigned short*)wt.data_ptr(),
-                             b ? b->data_ptr<float>() : nullptr,
-                             (unsigned short*)y.data_ptr(), Nb, C, H, W,
-                             Kout, R, S, OH, OW, (int)stride, (int)pad,
+        launch_conv_fwd_bf16(bfc(x), bfc(wt), bp, bfp(y), Nb, C, H,
+                             W, Kout, R, S, OH, OW, (int)stride, (int)pad,
                              relu ? 1 : 0, stream_of(x));
       return y;
     }
@@ -969,167 +701,144 @@ torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w,
   launch_wperm_crs_ko(w.data_ptr<float>(), wt.data_ptr<float>(), Kout, C,
                       R * S, stream_of(x));
   auto y = empty_cl({Nb, Kout, OH, OW}, x.options());
-  launch_conv_fwd(x.data_ptr<float>(), wt.data_ptr<float>(),
-                  b ? b->data_ptr<float>() : nullptr, y.data_ptr<float>(),
-                  Nb, C, H, W, Kout, R, S, OH, OW, (int)stride, (int)pad,
-                  relu ? 1 : 0, stream_of(x));
+  launch_conv_fwd(x.data_ptr<float>(), wt.data_ptr<float>(), bp,
+                  y.data_ptr<float>(), Nb, C, H, W, Kout, R, S, OH, OW,
+                  (int)stride, (int)pad, relu ? 1 : 0, stream_of(x));
   return y;
 }
 
 
-// bf16 dw dispatch: tap-accumulator kernel for the 3x3 s1 p1 ResNet
-// shapes (single-pass streaming), implicit-GEMM split-K otherwise
+// bf16 dw dispatch: tap-accumulator kernel for the 3x3 p1 ResNet shapes
+// (single-pass streaming; s1 and s2 forms share the launch plan and the
+// workspace), implicit-GEMM split-K otherwise
 static void bf16_dw(const torch::Tensor& dy, const torch::Tensor& x,
                     torch::Tensor& dw_target, const torch::Tensor& w,
                     int Nb, int C, int H, int W, int Kout, int R, int S,
                     int stride, int pad, void* st) {
-  if (conv_bwdw_tap_ok(C, H, W, Kout, R, S, stride, pad)) {
-    // image-group slabs + the two-stage combine's chunk sums, exactly as
-    // the launcher lays them out
+  auto f32 = w.options().dtype(torch::kFloat);
+  bool tap_s1 = conv_bwdw_tap_ok(C, H, W, Kout, R, S, stride, pad);
+  if (tap_s1 || conv_bwdw_tap_s2_ok(C, H, W, Kout, R, S, stride, pad)) {
     int SL = conv_bwdw_tap_ws_slabs(Nb, C, Kout, nullptr, nullptr, nullptr);
-    auto ws = torch::empty({(long)SL * Kout * C * 9},
-                           w.options().dtype(torch::kFloat));
-    launch_conv_bwdw_tap_bf16((const unsigned short*)dy.data_ptr(),
-                              (const unsigned short*)x.data_ptr(),
-                              dw_target.data_ptr<float>(),
-                              ws.data_ptr<float>(), Nb, C, H, W, Kout, st);
-    return;
-  }
-  if (conv_bwdw_tap_s2_ok(C, H, W, Kout, R, S, stride, pad)) {
-    int SL = conv_bwdw_tap_ws_slabs(Nb, C, Kout, nullptr, nullptr, nullptr);
-    auto ws = torch::empty({(long)SL * Kout * C * 9},
-                           w.options().dtype(torch::kFloat));
-    launch_conv_bwdw_tap_s2_bf16((const unsigned short*)dy.data_ptr(),
-                                 (const unsigned short*)x.data_ptr(),
-                                 dw_target.data_ptr<float>(),
-                                 ws.data_ptr<float>(), Nb, C, H, W, Kout,
-                                 st);
+    auto ws = torch::empty({(long)SL * Kout * C * 9}, f32);
+    auto launch = tap_s1 ? launch_conv_bwdw_tap_bf16
+                         : launch_conv_bwdw_tap_s2_bf16;
+    launch(bfc(dy), bfc(x), dw_target.data_ptr<float>(),
+           ws.data_ptr<float>(), Nb, C, H, W, Kout, st);
     return;
   }
   int Ncrs = C * R * S;
   int OH = dy.size(2), OW = dy.size(3);
   long Kd = (long)Nb * OH * OW;
   int SK = conv_bwd_weight_bf16_splitk(Kout, Ncrs, Kd);
-  auto ws = torch::empty(
-      {((long)SK + 1 + (SK > 16 ? (SK + 15) / 16 : 0)) * Kout * Ncrs},
-      w.options().dtype(torch::kFloat));
-  launch_conv_bwd_weight_bf16((const unsigned short*)dy.data_ptr(),
-                              (const unsigned short*)x.data_ptr(),
-                              dw_target.data_ptr<float>(),
+  auto ws = torch::empty({conv_dwperm_ws_floats(Kout, Ncrs, SK)}, f32);
+  launch_conv_bwd_weight_bf16(bfc(dy), bfc(x), dw_target.data_ptr<float>(),
                               ws.data_ptr<float>(), SK, Nb, C, H, W, Kout,
                               R, S, OH, OW, stride, pad, st);
 }
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_bwd(
-    torch::Tensor x, torch::Tensor w, torch::Tensor dy, int64_t stride,
-    int64_t pad, bool has_b, bool need_dx);
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_bwd(
-    torch::Tensor x, torch::Tensor w, torch::Tensor dy, int64_t stride,
-    int64_t pad, bool has_b, bool need_dx) {
-  TORCH_CHECK(x.is_cuda());
+// The one conv backward, fp32 and bf16: returns dx (undefined unless
+// need_dx, masked by relu_y > 0 when relu_y is given), writes dw into
+// dw_out and, when db_out is given, the bias gradient into it.  Thin bf16
+// layers (the first conv: C = 1, 3) run the fp32 kernels on casts.
+static torch::Tensor conv_bwd_core(torch::Tensor x, torch::Tensor w,
+                                   torch::Tensor dy, int64_t stride,
+                                   int64_t pad, bool need_dx,
+                                   torch::Tensor dw_out,
+                                   c10::optional<torch::Tensor> db_out,
+                                   c10::optional<torch::Tensor> relu_y) {
   x = cl(x, "conv_bwd.x");
   w = w.contiguous();
   dy = cl(dy, "conv_bwd.dy");
   int Nb = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   int Kout = w.size(0), R = w.size(2), S = w.size(3);
   int OH = dy.size(2), OW = dy.size(3);
+  int st_ = (int)stride, pd = (int)pad;
   auto st = stream_of(x);
-
-  if (is_bf16(x)) {
-    bool fast = (Kout % 32) == 0 && (C % 8) == 0;
-    if (!fast) {
-      // fp32 fallback for the tiny first layers
-      auto r32 = conv2d_bwd(x.to(torch::kFloat), w, dy.to(torch::kFloat),
-                            stride, pad, has_b, need_dx);
-      auto dx32 = std::get<0>(r32);
-      return {dx32.defined() ? dx32.to(torch::kBFloat16) : dx32,
-              std::get<1>(r32), std::get<2>(r32)};
-    }
-    torch::Tensor dxb;
-    if (need_dx) {
-      auto wp = torch::empty({(long)Kout * R * S, C},
-                             w.options().dtype(torch::kBFloat16));
-      launch_wperm_rsko_c_bf16(w.data_ptr<float>(),
-                               (unsigned short*)wp.data_ptr(), Kout, C,
-                               R * S, st);
-      dxb = empty_cl({Nb, C, H, W}, x.options());
-      if (conv_tap_fwd_w4_ok(Kout, H, W, C, R, S, (int)stride, (int)pad))
-        launch_conv_tap_fwd_w4_bf16(
-            (const unsigned short*)dy.data_ptr(),
-            (const unsigned short*)wp.data_ptr(), nullptr,
-            (unsigned short*)dxb.data_ptr(), nullptr, Nb, Kout, C, 0, 1,
-            st);
-      else if (conv_tap_fwd_ok(Kout, H, W, C, R, S, (int)stride, (int)pad))
-        // bwd-data == the same correlation over dy with flipped taps
-        launch_conv_tap_fwd_bf16((const unsigned short*)dy.data_ptr(),
-                                 (const unsigned short*)wp.data_ptr(),
-                                 nullptr, (unsigned short*)dxb.data_ptr(),
-                                 nullptr, Nb, Kout, H, W, C, 0, 1, st);
-      else if (conv_tap_bwdd_s2_ok(C, H, W, Kout, R, S, (int)stride,
-                                   (int)pad))
-        launch_conv_tap_bwdd_s2_bf16(
-            (const unsigned short*)dy.data_ptr(),
-            (const unsigned short*)wp.data_ptr(),
-            (unsigned short*)dxb.data_ptr(), nullptr, Nb, Kout, H, W, C,
-            st);
-      else
-        launch_conv_bwd_data_bf16((const unsigned short*)dy.data_ptr(),
-                                  (const unsigned short*)wp.data_ptr(),
-                                  (unsigned short*)dxb.data_ptr(), Nb, C,
-                                  H, W, Kout, R, S, OH, OW, (int)stride,
-                                  (int)pad, st);
-    }
-    auto dw = torch::empty_like(w);
-    bf16_dw(dy, x, dw, w, Nb, C, H, W, Kout, R, S, (int)stride, (int)pad,
-            st);
-    torch::Tensor db;
-    if (has_b) {
-      db = torch::empty({Kout}, w.options());
-      auto parts = torch::empty({(long)Kout * 4096}, w.options());
-      launch_conv_db_bf16((const unsigned short*)dy.data_ptr(),
-                          db.data_ptr<float>(), parts.data_ptr<float>(), Nb,
-                          Kout, OH * OW, st);
-    }
-    return {dxb, dw, db};
+  const bool bf = is_bf16(x);
+  if (bf && !((Kout % 32) == 0 && (C % 8) == 0)) {
+    auto dx32 = conv_bwd_core(
+        x.to(torch::kFloat), w, dy.to(torch::kFloat), stride, pad, need_dx,
+        dw_out, db_out,
+        relu_y ? c10::optional<torch::Tensor>(relu_y->to(torch::kFloat))
+               : c10::nullopt);
+    return dx32.defined() ? dx32.to(torch::kBFloat16) : dx32;
   }
 
   torch::Tensor dx;
   if (need_dx) {
-    auto wp = torch::empty({(long)Kout * R * S, C}, w.options());
-    launch_wperm_kors_c(w.data_ptr<float>(), wp.data_ptr<float>(), Kout, C,
-                        R * S, st);
+    auto wp = torch::empty(
+        {(long)Kout * R * S, C},
+        bf ? w.options().dtype(torch::kBFloat16) : w.options());
+    if (bf)
+      launch_wperm_rsko_c_bf16(w.data_ptr<float>(), bfp(wp), Kout, C, R * S,
+                               st);
+    else
+      launch_wperm_kors_c(w.data_ptr<float>(), wp.data_ptr<float>(), Kout,
+                          C, R * S, st);
     dx = empty_cl({Nb, C, H, W}, x.options());
-    launch_conv_bwd_data(dy.data_ptr<float>(), wp.data_ptr<float>(),
-                         dx.data_ptr<float>(), Nb, C, H, W, Kout, R, S, OH,
-                         OW, (int)stride, (int)pad, st);
-  } else {
-    dx = torch::Tensor();
+    torch::Tensor ryt;
+    if (relu_y) ryt = cl(*relu_y, "conv_bwd.relu_y");
+    if (!bf) {
+      launch_conv_bwd_data_relu(
+          dy.data_ptr<float>(), wp.data_ptr<float>(), dx.data_ptr<float>(),
+          relu_y ? ryt.data_ptr<float>() : nullptr, Nb, C, H, W, Kout, R, S,
+          OH, OW, st_, pd, st);
+    } else {
+      const unsigned short* ry = relu_y ? bfc(ryt) : nullptr;
+      if (conv_tap_fwd_w4_ok(Kout, H, W, C, R, S, st_, pd))
+        launch_conv_tap_fwd_w4_bf16(bfc(dy), bfc(wp), nullptr, bfp(dx), ry,
+                                    Nb, Kout, C, 0, 1, st);
+      else if (conv_tap_fwd_ok(Kout, H, W, C, R, S, st_, pd))
+        // bwd-data == the same correlation over dy with flipped taps
+        launch_conv_tap_fwd_bf16(bfc(dy), bfc(wp), nullptr, bfp(dx), ry, Nb,
+                                 Kout, H, W, C, 0, 1, st);
+      else if (conv_tap_bwdd_s2_ok(C, H, W, Kout, R, S, st_, pd))
+        launch_conv_tap_bwdd_s2_bf16(bfc(dy), bfc(wp), bfp(dx), ry, Nb, Kout,
+                                     H, W, C, st);
+      else
+        launch_conv_bwd_data_bf16_relu(bfc(dy), bfc(wp), bfp(dx), ry, Nb, C,
+                                       H, W, Kout, R, S, OH, OW, st_, pd,
+                                       st);
+    }
   }
 
-  int Ncrs = C * R * S;
-  long Kdim = (long)Nb * OH * OW;
-  int SK = conv_bwd_weight_splitk(Kout, Ncrs, Kdim);
+  if (bf) {
+    bf16_dw(dy, x, dw_out, w, Nb, C, H, W, Kout, R, S, st_, pd, st);
+  } else {
+    int Ncrs = C * R * S;
+    long Kdim = (long)Nb * OH * OW;
+    int SK = conv_bwd_weight_splitk(Kout, Ncrs, Kdim);
+    auto ws = torch::empty({conv_bwd_weight_ws_floats(Kout, Ncrs, SK)},
+                           w.options());
+    launch_conv_bwd_weight(dy.data_ptr<float>(), x.data_ptr<float>(),
+                           dw_out.data_ptr<float>(), ws.data_ptr<float>(),
+                           SK, Nb, C, H, W, Kout, R, S, OH, OW, st_, pd, st);
+  }
+
+  if (db_out) {
+    TORCH_CHECK(db_out->is_contiguous() && db_out->numel() == Kout);
+    auto parts = torch::empty({conv_db_ws_floats(Kout)}, w.options());
+    if (bf)
+      launch_conv_db_bf16(bfc(dy), db_out->data_ptr<float>(),
+                          parts.data_ptr<float>(), Nb, Kout, OH * OW, st);
+    else
+      launch_conv_db(dy.data_ptr<float>(), db_out->data_ptr<float>(),
+                     parts.data_ptr<float>(), Nb, Kout, OH * OW, st);
+  }
+  return dx;
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_bwd(
+    torch::Tensor x, torch::Tensor w, torch::Tensor dy, int64_t stride,
+    int64_t pad, bool has_b, bool need_dx) {
+  TORCH_CHECK(x.is_cuda());
+  w = w.contiguous();
   auto dw = torch::empty_like(w);
-  // ws: SK slabs + one rsc-ordered temp; the small-Ncrs direct path uses
-  // 512 chunk partials instead
-  long ws_mult = (Ncrs <= 32 && Kout <= 64)
-                     ? 2049
-                     : (long)SK + 1 + (SK > 16 ? (SK + 15) / 16 : 0);
-  auto ws = torch::empty({ws_mult * Kout * Ncrs}, w.options());
-  launch_conv_bwd_weight(dy.data_ptr<float>(), x.data_ptr<float>(),
-                         dw.data_ptr<float>(), ws.data_ptr<float>(), SK, Nb,
-                         C, H, W, Kout, R, S, OH, OW, (int)stride, (int)pad,
-                         st);
-
   torch::Tensor db;
-  if (has_b) {
-    db = torch::empty({Kout}, dy.options());
-    auto parts = torch::empty({(long)Kout * 4096}, dy.options());
-    launch_conv_db(dy.data_ptr<float>(), db.data_ptr<float>(),
-                   parts.data_ptr<float>(), Nb, Kout, OH * OW, st);
-  } else {
-    db = torch::Tensor();
-  }
+  if (has_b) db = torch::empty({w.size(0)}, w.options());
+  auto dx = conv_bwd_core(
+      x, w, dy, stride, pad, need_dx, dw,
+      has_b ? c10::optional<torch::Tensor>(db) : c10::nullopt, c10::nullopt);
   return {dx, dw, db};
 }
 
@@ -1138,8 +847,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> conv2d_bwd(
 // weight/bias gradients written straight into their flat_grads slices,
 // autograd's per-param accumulate-add and the zero-grad fill disappear.
 // Assignment into the view is bitwise-identical to autograd's
-// accumulate-into-zeroed-grad.  fp32 only (the bf16 ResNet path keeps
-// autograd this round).
+// accumulate-into-zeroed-grad.  fp32 only.
 
 torch::Tensor conv2d_bwd_into(torch::Tensor x, torch::Tensor w,
                               torch::Tensor dy, int64_t stride, int64_t pad,
@@ -1148,55 +856,12 @@ torch::Tensor conv2d_bwd_into(torch::Tensor x, torch::Tensor w,
                               c10::optional<torch::Tensor> relu_y) {
   TORCH_CHECK(x.is_cuda() && !is_bf16(x));
   TORCH_CHECK(dw_out.is_contiguous() && dw_out.numel() == w.numel());
-  x = cl(x, "conv_bwd.x");
-  w = w.contiguous();
-  dy = cl(dy, "conv_bwd.dy");
-  int Nb = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  int Kout = w.size(0), R = w.size(2), S = w.size(3);
-  int OH = dy.size(2), OW = dy.size(3);
-  auto st = stream_of(x);
-
-  torch::Tensor dx;
-  if (need_dx) {
-    auto wp = torch::empty({(long)Kout * R * S, C}, w.options());
-    launch_wperm_kors_c(w.data_ptr<float>(), wp.data_ptr<float>(), Kout, C,
-                        R * S, st);
-    dx = empty_cl({Nb, C, H, W}, x.options());
-    const float* ry = nullptr;
-    torch::Tensor ryt;
-    if (relu_y) {
-      ryt = cl(*relu_y, "conv_bwd.relu_y");
-      ry = ryt.data_ptr<float>();
-    }
-    launch_conv_bwd_data_relu(dy.data_ptr<float>(), wp.data_ptr<float>(),
-                              dx.data_ptr<float>(), ry, Nb, C, H, W, Kout,
-                              R, S, OH, OW, (int)stride, (int)pad, st);
-  }
-
-  int Ncrs = C * R * S;
-  long Kdim = (long)Nb * OH * OW;
-  int SK = conv_bwd_weight_splitk(Kout, Ncrs, Kdim);
-  long ws_mult = (Ncrs <= 32 && Kout <= 64)
-                     ? 2049
-                     : (long)SK + 1 + (SK > 16 ? (SK + 15) / 16 : 0);
-  auto ws = torch::empty({ws_mult * Kout * Ncrs}, w.options());
-  launch_conv_bwd_weight(dy.data_ptr<float>(), x.data_ptr<float>(),
-                         dw_out.data_ptr<float>(), ws.data_ptr<float>(), SK,
-                         Nb, C, H, W, Kout, R, S, OH, OW, (int)stride,
-                         (int)pad, st);
-
-  if (db_out) {
-    TORCH_CHECK(db_out->is_contiguous() && db_out->numel() == Kout);
-    auto parts = torch::empty({(long)Kout * 4096}, dy.options());
-    launch_conv_db(dy.data_ptr<float>(), db_out->data_ptr<float>(),
-                   parts.data_ptr<float>(), Nb, Kout, OH * OW, st);
-  }
-  return dx;
+  return conv_bwd_core(x, w, dy, stride, pad, need_dx, dw_out, db_out,
+                       relu_y);
 }
 
 // bf16/fp32 conv backward with dw written into a caller-owned view and
-// no bias (the ResNet tape: conv layers are bias-free).  Falls back to
-// the fp32 kernels with casts for the thin first layer, like conv2d_bwd.
+// no bias (the ResNet tape: conv layers are bias-free).
 torch::Tensor conv2d_bwd_wdx_into(torch::Tensor x, torch::Tensor w,
                                   torch::Tensor dy, int64_t stride,
                                   int64_t pad, bool need_dx,
@@ -1204,66 +869,8 @@ torch::Tensor conv2d_bwd_wdx_into(torch::Tensor x, torch::Tensor w,
                                   c10::optional<torch::Tensor> relu_y) {
   TORCH_CHECK(x.is_cuda());
   TORCH_CHECK(dw_out.is_contiguous() && dw_out.numel() == w.numel());
-  if (!is_bf16(x)) {
-    return conv2d_bwd_into(x, w, dy, stride, pad, need_dx, dw_out,
-                           c10::nullopt, relu_y);
-  }
-  x = cl(x, "conv_bwd.x");
-  w = w.contiguous();
-  dy = cl(dy, "conv_bwd.dy");
-  int Nb = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  int Kout = w.size(0), R = w.size(2), S = w.size(3);
-  int OH = dy.size(2), OW = dy.size(3);
-  auto st = stream_of(x);
-  bool fast = (Kout % 32) == 0 && (C % 8) == 0;
-  if (!fast) {
-    auto dx32 = conv2d_bwd_into(
-        x.to(torch::kFloat), w, dy.to(torch::kFloat), stride, pad, need_dx,
-        dw_out, c10::nullopt,
-        relu_y ? c10::optional<torch::Tensor>(relu_y->to(torch::kFloat))
-               : c10::nullopt);
-    return dx32.defined() ? dx32.to(torch::kBFloat16) : dx32;
-  }
-  torch::Tensor dxb;
-  if (need_dx) {
-    auto wp = torch::empty({(long)Kout * R * S, C},
-                           w.options().dtype(torch::kBFloat16));
-    launch_wperm_rsko_c_bf16(w.data_ptr<float>(),
-                             (unsigned short*)wp.data_ptr(), Kout, C, R * S,
-                             st);
-    dxb = empty_cl({Nb, C, H, W}, x.options());
-    const unsigned short* ry = nullptr;
-    torch::Tensor ryt;
-    if (relu_y) {
-      ryt = cl(*relu_y, "conv_bwd.relu_y");
-      ry = (const unsigned short*)ryt.data_ptr();
-    }
-    if (conv_tap_fwd_w4_ok(Kout, H, W, C, R, S, (int)stride, (int)pad))
-      launch_conv_tap_fwd_w4_bf16((const unsigned short*)dy.data_ptr(),
-                                  (const unsigned short*)wp.data_ptr(),
-                                  nullptr, (unsigned short*)dxb.data_ptr(),
-                                  ry, Nb, Kout, C, 0, 1, st);
-    else if (conv_tap_fwd_ok(Kout, H, W, C, R, S, (int)stride, (int)pad))
-      launch_conv_tap_fwd_bf16((const unsigned short*)dy.data_ptr(),
-                               (const unsigned short*)wp.data_ptr(),
-                               nullptr, (unsigned short*)dxb.data_ptr(),
-                               ry, Nb, Kout, H, W, C, 0, 1, st);
-    else if (conv_tap_bwdd_s2_ok(C, H, W, Kout, R, S, (int)stride,
-                                 (int)pad))
-      launch_conv_tap_bwdd_s2_bf16((const unsigned short*)dy.data_ptr(),
-                                   (const unsigned short*)wp.data_ptr(),
-                                   (unsigned short*)dxb.data_ptr(), ry, Nb,
-                                   Kout, H, W, C, st);
-    else
-      launch_conv_bwd_data_bf16_relu(
-          (const unsigned short*)dy.data_ptr(),
-          (const unsigned short*)wp.data_ptr(),
-          (unsigned short*)dxb.data_ptr(), ry, Nb, C, H, W, Kout, R, S, OH,
-          OW, (int)stride, (int)pad, st);
-  }
-  bf16_dw(dy, x, dw_out, w, Nb, C, H, W, Kout, R, S, (int)stride,
-          (int)pad, st);
-  return dxb;
+  return conv_bwd_core(x, w, dy, stride, pad, need_dx, dw_out, c10::nullopt,
+                       relu_y);
 }
 
 // ------------------------------------------------------------- batchnorm
@@ -1282,13 +889,11 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> batchnorm_fwd(
   auto scratch = torch::empty({(long)bn_scratch_floats(C)},
                               x.options().dtype(torch::kFloat));
   if (is_bf16(x))
-    launch_bn_fwd_bf16((const unsigned short*)x.data_ptr(),
-                       w.data_ptr<float>(), b.data_ptr<float>(),
+    launch_bn_fwd_bf16(bfc(x), w.data_ptr<float>(), b.data_ptr<float>(),
                        running_mean.data_ptr<float>(),
                        running_var.data_ptr<float>(),
                        save_mean.data_ptr<float>(),
-                       save_rstd.data_ptr<float>(),
-                       (unsigned short*)y.data_ptr(),
+                       save_rstd.data_ptr<float>(), bfp(y),
                        scratch.data_ptr<float>(), Nb, C, HW,
                        (float)momentum, (float)eps, training ? 1 : 0,
                        relu ? 1 : 0, stream_of(x));
@@ -1303,38 +908,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> batchnorm_fwd(
   return {y, save_mean, save_rstd};
 }
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> batchnorm_bwd(
-    torch::Tensor x, torch::Tensor w, torch::Tensor save_mean,
-    torch::Tensor save_rstd, torch::Tensor dy) {
-  TORCH_CHECK(x.is_cuda());
-  x = cl(x, "bn_bwd.x");
-  dy = cl(dy, "bn_bwd.dy");
-  int Nb = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
-  auto dx = empty_cl({x.size(0), x.size(1), x.size(2), x.size(3)},
-                     x.options());
-  auto dw = torch::empty({C}, x.options().dtype(torch::kFloat));
-  auto db = torch::empty({C}, x.options().dtype(torch::kFloat));
-  auto scratch = torch::empty({(long)bn_scratch_floats(C)},
-                              x.options().dtype(torch::kFloat));
-  if (is_bf16(x))
-    launch_bn_bwd_bf16((const unsigned short*)x.data_ptr(),
-                       (const unsigned short*)dy.data_ptr(),
-                       w.data_ptr<float>(), save_mean.data_ptr<float>(),
-                       save_rstd.data_ptr<float>(),
-                       scratch.data_ptr<float>(),
-                       (unsigned short*)dx.data_ptr(),
-                       dw.data_ptr<float>(), db.data_ptr<float>(), Nb, C,
-                       HW, 1, stream_of(x));
-  else
-    launch_bn_bwd(x.data_ptr<float>(), dy.data_ptr<float>(),
-                  w.data_ptr<float>(), save_mean.data_ptr<float>(),
-                  save_rstd.data_ptr<float>(), scratch.data_ptr<float>(),
-                  dx.data_ptr<float>(), dw.data_ptr<float>(),
-                  db.data_ptr<float>(), Nb, C, HW, 1, stream_of(x));
-  return {dx, dw, db};
-}
-
-// manual-tape variant: dw/db written into caller-owned flat-grad views
+// dw/db written into caller-owned tensors (manual tape: flat-grad views)
 torch::Tensor batchnorm_bwd_into(torch::Tensor x, torch::Tensor w,
                                  torch::Tensor save_mean,
                                  torch::Tensor save_rstd, torch::Tensor dy,
@@ -1350,12 +924,10 @@ torch::Tensor batchnorm_bwd_into(torch::Tensor x, torch::Tensor w,
   auto scratch = torch::empty({(long)bn_scratch_floats(C)},
                               x.options().dtype(torch::kFloat));
   if (is_bf16(x))
-    launch_bn_bwd_bf16((const unsigned short*)x.data_ptr(),
-                       (const unsigned short*)dy.data_ptr(),
-                       w.data_ptr<float>(), save_mean.data_ptr<float>(),
+    launch_bn_bwd_bf16(bfc(x), bfc(dy), w.data_ptr<float>(),
+                       save_mean.data_ptr<float>(),
                        save_rstd.data_ptr<float>(),
-                       scratch.data_ptr<float>(),
-                       (unsigned short*)dx.data_ptr(),
+                       scratch.data_ptr<float>(), bfp(dx),
                        dw_out.data_ptr<float>(), db_out.data_ptr<float>(),
                        Nb, C, HW, 1, stream_of(x));
   else
@@ -1365,6 +937,16 @@ torch::Tensor batchnorm_bwd_into(torch::Tensor x, torch::Tensor w,
                   dx.data_ptr<float>(), dw_out.data_ptr<float>(),
                   db_out.data_ptr<float>(), Nb, C, HW, 1, stream_of(x));
   return dx;
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> batchnorm_bwd(
+    torch::Tensor x, torch::Tensor w, torch::Tensor save_mean,
+    torch::Tensor save_rstd, torch::Tensor dy) {
+  auto f32 = x.options().dtype(torch::kFloat);
+  auto dw = torch::empty({x.size(1)}, f32);
+  auto db = torch::empty({x.size(1)}, f32);
+  auto dx = batchnorm_bwd_into(x, w, save_mean, save_rstd, dy, dw, db);
+  return {dx, dw, db};
 }
 
 // ---------------------------------------------------------------- poison
@@ -1449,7 +1031,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("apply_update", &apply_update);
   m.def("agg_orderstat", &agg_orderstat);
   m.def("orderstat_rlr_apply", &orderstat_rlr_apply);
-  m.def("orderstat_max_k", []() { return orderstat_max_k(); });
+  m.def("orderstat_max_k", &orderstat_max_k);
   m.def("add_noise", &add_noise);
   m.def("gemm", &gemm);
   m.def("gemm_bf16", &gemm_bf16);
@@ -1464,8 +1046,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dropout_relu_bwd", &dropout_relu_bwd);
   m.def("batchnorm_bwd_into", &batchnorm_bwd_into);
   m.def("conv2d_bwd_wdx_into", &conv2d_bwd_wdx_into);
+  // host arithmetic only, exported so a test without a GPU can pin it:
+  // the split-K pickers and the workspace size (in floats) each op
+  // allocates for its launcher
+  m.def("gemm_f32_splitk", &gemm_f32_splitk);
+  m.def("conv_bwd_weight_splitk", &conv_bwd_weight_splitk);
+  m.def("conv_bwd_weight_bf16_splitk", &conv_bwd_weight_bf16_splitk);
+  m.def("conv_db_chunks", &conv_db_chunks);
+  m.def("gemm_splitk_ws_floats", &gemm_splitk_ws_floats);
+  m.def("conv_bwd_weight_ws_floats", &conv_bwd_weight_ws_floats);
+  m.def("conv_dwperm_ws_floats", &conv_dwperm_ws_floats);
+  m.def("conv_db_ws_floats", &conv_db_ws_floats);
+  m.def("flat_norm_scratch_floats", &flat_norm_scratch_floats);
   // (S, G, chunks, slabs): the tap bwd-weight launch plan and the
-  // workspace slabs bf16_dw allocates for it (host arithmetic only)
+  // workspace slabs bf16_dw allocates for it
   m.def("conv_bwdw_tap_ws_slabs", [](int64_t Nb, int64_t C, int64_t Kout) {
     int S, G, chunks;
     int slabs = conv_bwdw_tap_ws_slabs((int)Nb, (int)C, (int)Kout, &S, &G,

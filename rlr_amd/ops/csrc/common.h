@@ -25,6 +25,14 @@ static inline int grid_for(long n, int block = kBlock, int cap = kMaxBlocks) {
   return (int)(b < cap ? (b > 0 ? b : 1) : cap);
 }
 
+// Deep split-K (SK > kSplitKFold) combines in two stages: stage 1 folds
+// the SK slabs kSplitKFold at a time into this many extra slabs, which
+// every split-K workspace carries after its own slabs.
+constexpr int kSplitKFold = 16;
+static inline int splitk_stage1_slabs(int SK) {
+  return SK > kSplitKFold ? (SK + kSplitKFold - 1) / kSplitKFold : 0;
+}
+
 // ------------------------------------------------------------------ philox
 // Philox4x32-10 counter-based RNG (deterministic: (seed, offset, idx) ->
 // 4 x uint32).  Used for dropout masks and server DP noise so results are

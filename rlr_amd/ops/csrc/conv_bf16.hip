@@ -12,6 +12,7 @@
 // C % 4 == 0; bwd-weight C % 8 == 0.  First layers (C=1,3) take the fp32
 // fallback — they are a rounding error of ResNet's FLOPs.
 #include "common.h"
+#include "launchers.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
@@ -578,10 +579,6 @@ __global__ void conv_db_bf16_stage1_k(const unsigned short* __restrict__ dy,
 }
 
 extern "C" {
-void launch_splitk_reduce(const float* ws, float* C, const float* bias,
-                          int M, int N, int ldc, int SK, int relu, void* s);
-int conv_bwd_weight_splitk(int Kout, int Ncrs, long Kdim);
-
 // bf16 split-K policy: target ~2304 blocks (9/CU queued) — the SK sweep
 // on MI355X showed the f32 path's 1024-block target leaves 10-20% on the
 // table for every ResNet layer shape (tests/perf/bwdw_micro)
@@ -593,9 +590,6 @@ int conv_bwd_weight_bf16_splitk(int Kout, int Ncrs, long Kdim) {
   long sk = want < max_chunks ? want : max_chunks;
   return (int)(sk < 1 ? 1 : (sk > 256 ? 256 : sk));
 }
-void launch_dwperm_rsc_crs(const float*, float*, int, int, int, void*);
-void launch_conv_db_stage2(const float*, float*, int, int, void*);
-int conv_db_chunks(long M, int Kout);
 
 void launch_conv_fwd_bf16(const unsigned short* x, const unsigned short* wt,
                           const float* bias, unsigned short* y, int Nb,
@@ -648,6 +642,7 @@ void launch_conv_bwd_data_bf16(const unsigned short* dy,
 }
 
 // variant 0: 64-wide tile depth-2; 1: 128-wide; 2: 64-wide depth-3 ring
+// ws: conv_dwperm_ws_floats(Kout, Ncrs, SK) floats (conv_f32.hip)
 void launch_conv_bwd_weight_bf16_ex(const unsigned short* dy,
                                     const unsigned short* x, float* dw,
                                     float* ws, int SK, int variant, int Nb,
@@ -687,10 +682,7 @@ void launch_conv_bwd_weight_bf16_ex(const unsigned short* dy,
       conv_bwd_weight_bf16_k<false, 64, 2><<<grid, 256, 0, st>>>(
           dy, x, target, sh, Ncrs, k_per_chunk, SK == 1);
   }
-  extern void launch_splitk_reduce_dwperm(const float*, float*, int, int,
-                                          int, int, void*);
-  launch_splitk_reduce_dwperm(SK == 1 ? rsc : slabs, dw, Kout, C, R * S, SK,
-                              s);
+  launch_splitk_reduce_dwperm(target, dw, Kout, C, R * S, SK, s);
 }
 
 void launch_conv_bwd_weight_bf16(const unsigned short* dy,
@@ -715,6 +707,7 @@ void launch_wperm_rsko_c_bf16(const float* w, unsigned short* out, int Kout,
                         (hipStream_t)s>>>(w, out, Kout, C, RS);
 }
 
+// partials: conv_db_ws_floats(Kout) floats (conv_f32.hip)
 void launch_conv_db_bf16(const unsigned short* dy, float* db,
                          float* partials, int Nb, int Kout, int OHW,
                          void* s) {

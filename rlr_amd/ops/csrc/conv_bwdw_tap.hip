@@ -27,6 +27,7 @@
 //   grid = (Kout/32, C/32, S);  S image-groups bound the slab memory for
 //   the deep 512-channel layers.
 #include "common.h"
+#include "launchers.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
@@ -246,7 +247,7 @@ int conv_bwdw_tap_ok(int C, int H, int W, int Kout, int R, int S,
 }
 
 // number of image-group slabs (bounds ws to ~64 MB of fp32 partials)
-int conv_bwdw_tap_slabs(int Nb, int C, int Kout) {
+static int conv_bwdw_tap_slabs(int Nb, int C, int Kout) {
   long kc9 = (long)Kout * C * 9 * 4;
   long s = (64L << 20) / kc9;
   if (s < 1) s = 1;

@@ -19,6 +19,7 @@
 // Weight transforms (tiny, per call): fwd wt[(r,s,c)][ko], bwd-data
 // wp[(r,s,ko)][c].  All reductions fixed-order; no atomics.
 #include "common.h"
+#include "launchers.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -1250,10 +1251,6 @@ __global__ void wperm_rsko_c_k(const float* __restrict__ w,
   }
 }
 
-extern "C" void launch_splitk_reduce(const float* ws, float* C,
-                                     const float* bias, int M, int N,
-                                     int ldc, int SK, int relu, void* s);
-
 extern "C" {
 void launch_conv_fwd(const float* x, const float* wt, const float* bias,
                      float* y, int Nb, int C, int H, int W, int Kout, int R,
@@ -1359,7 +1356,23 @@ int conv_bwd_weight_splitk(int Kout, int Ncrs, long Kdim) {
   return (int)(sk < 1 ? 1 : (sk > 192 ? 192 : sk));
 }
 
-// ws: SK*Kout*Ncrs + Kout*Ncrs floats (split-K slabs + rsc-ordered temp)
+// Small layers (the thin first conv) take the direct chunked kernel
+// instead of the split-K implicit GEMM: at most kSmallBwdwMaxChunks
+// m-chunks, each writing one Kout*Ncrs slab of partials.
+constexpr int kSmallBwdwMaxChunks = 2048;
+static bool conv_bwdw_small(int Kout, int Ncrs) {
+  return Ncrs <= 32 && Kout <= 64;
+}
+
+// Workspace of launch_conv_bwd_weight: the chunk partials of the small
+// path, the split-K layout of conv_dwperm_ws_floats otherwise.
+long conv_bwd_weight_ws_floats(int Kout, int Ncrs, int SK) {
+  if (conv_bwdw_small(Kout, Ncrs))
+    return (long)kSmallBwdwMaxChunks * Kout * Ncrs;
+  return conv_dwperm_ws_floats(Kout, Ncrs, SK);
+}
+
+// ws: conv_bwd_weight_ws_floats(Kout, Ncrs, SK) floats
 void launch_conv_bwd_weight(const float* dy, const float* x, float* dw,
                             float* ws, int SK, int Nb, int C, int H, int W,
                             int Kout, int R, int S, int OH, int OW,
@@ -1371,11 +1384,11 @@ void launch_conv_bwd_weight(const float* dy, const float* x, float* dw,
       SK == 1 ? Kdim : (((Kdim + SK - 1) / SK + BK - 1) / BK) * BK;
   dim3 grid((Kout + 63) / 64, (Ncrs + BN - 1) / BN, SK);
   hipStream_t st = (hipStream_t)s;
-  if (Ncrs <= 32 && Kout <= 64) {
+  if (conv_bwdw_small(Kout, Ncrs)) {
     // one 128-row tile per block where possible: 512 fixed chunks left the
     // chip at 2 blocks/CU (48 KB LDS, 4 waves) — finer chunking trades a
     // longer fixed-order reduce for 3x the resident parallelism
-    int chunks = (int)min((Kdim + 127) / 128, (long)2048);
+    int chunks = (int)min((Kdim + 127) / 128, (long)kSmallBwdwMaxChunks);
     if (chunks < 64) chunks = 64;
     long kpc = ((Kdim + chunks - 1) / chunks + 127) / 128 * 128;
     conv_small_bwdw_k<128><<<chunks, 256, 0, st>>>(dy, x, ws, sh, Ncrs,
@@ -1403,31 +1416,24 @@ void launch_conv_bwd_weight(const float* dy, const float* x, float* dw,
     conv_bwd_weight_k<false, false><<<grid, 256, 0, st>>>(
         dy, x, target, sh, Ncrs, k_per_chunk, SK == 1);
   // fused combine+permute (for SK==1 it degenerates to the permute of
-  // the directly-written rsc tensor); deep SK first folds 16-slab chunks
-  // with a parallel stage-1 into the extra workspace slabs
-  long n_out = (long)Kout * Ncrs;
-  if (SK > 16) {
-    extern void launch_splitk_partial(const float*, float*, long, int,
-                                      int, void*);
-    int chunks = (SK + 15) / 16;
-    float* ws2 = slabs + (long)SK * n_out + n_out;  // after slabs + rsc
-    launch_splitk_partial(slabs, ws2, n_out, SK, 16, s);
-    splitk_reduce_dwperm_k<<<grid_for(n_out), kBlock, 0, st>>>(
-        ws2, dw, Kout, C, R * S, chunks);
-  } else {
-    splitk_reduce_dwperm_k<<<grid_for(n_out), kBlock, 0, st>>>(
-        SK == 1 ? rsc : slabs, dw, Kout, C, R * S, SK);
-  }
+  // the directly-written rsc tensor)
+  launch_splitk_reduce_dwperm(target, dw, Kout, C, R * S, SK, s);
 }
+
+constexpr int kConvDbMaxChunks = 4096;
 
 int conv_db_chunks(long M, int Kout) {
   long want = 131072 / (Kout < 1 ? 1 : Kout);   // ~128k threads
   long cap = (M + 63) / 64;                     // >= 64 rows per chunk
   long c = want < cap ? want : cap;
   if (c < 64) c = 64;
-  if (c > 4096) c = 4096;
+  if (c > kConvDbMaxChunks) c = kConvDbMaxChunks;
   return (int)c;
 }
+
+// Partials of launch_conv_db and launch_conv_db_bf16: one Kout row per
+// chunk, sized for the most chunks conv_db_chunks can return.
+long conv_db_ws_floats(int Kout) { return (long)kConvDbMaxChunks * Kout; }
 
 static int conv_db_kblk(int Kout) {
   if (Kout >= kBlock) return kBlock;
@@ -1447,15 +1453,22 @@ void launch_conv_db(const float* dy, float* db, float* partials, int Nb,
   conv_db_stage2_k<<<Kout, kBlock, 0, st>>>(partials, db, Kout, chunks);
 }
 
+// The conv backward-weight split-K workspace, fp32 and bf16: SK slabs of
+// Kout*Ncrs partials, one rsc-ordered temp (the direct target when
+// SK == 1), then the stage-1 slabs of a deep split.
+long conv_dwperm_ws_floats(int Kout, int Ncrs, int SK) {
+  return (long)(SK + 1 + splitk_stage1_slabs(SK)) * Kout * Ncrs;
+}
+
+// ws: the first slab of a conv_dwperm_ws_floats workspace when SK > 1,
+// its rsc temp when SK == 1
 void launch_splitk_reduce_dwperm(const float* ws, float* dw, int Kout,
                                  int C, int RS, int SK, void* s) {
   long n_out = (long)Kout * C * RS;
-  if (SK > 16) {  // caller provides the stage-1 slabs after slabs + rsc
-    extern void launch_splitk_partial(const float*, float*, long, int, int,
-                                      void*);
-    int chunks = (SK + 15) / 16;
+  if (SK > kSplitKFold) {  // fold into the stage-1 slabs after slabs + rsc
+    int chunks = splitk_stage1_slabs(SK);
     float* ws2 = const_cast<float*>(ws) + (long)(SK + 1) * n_out;
-    launch_splitk_partial(ws, ws2, n_out, SK, 16, s);
+    launch_splitk_partial(ws, ws2, n_out, SK, kSplitKFold, s);
     splitk_reduce_dwperm_k<<<grid_for(n_out), kBlock, 0, (hipStream_t)s>>>(
         ws2, dw, Kout, C, RS, chunks);
     return;

@@ -5,6 +5,7 @@
 // All memory-bound: float4-vectorized grid-stride loops at the HBM roofline
 // (cdna_hip_programming.md Appendix B, Guideline 13).
 #include "common.h"
+#include "launchers.h"
 
 // ---------------------------------------------------------------- relu
 

@@ -5,6 +5,7 @@
 // are two-stage (block partials -> single-block finalize) for run-to-run
 // determinism (no float atomics).
 #include "common.h"
+#include "launchers.h"
 
 constexpr int kNPart = 1024;  // fixed partial count -> deterministic sum
 
@@ -104,9 +105,12 @@ __global__ void delta64_k(const float* __restrict__ p,
 }
 
 extern "C" {
+// scratch of launch_clipped_sgd and launch_pgd_project: kNPart partials,
+// then the one scale the update kernel reads
+long flat_norm_scratch_floats() { return kNPart + 1; }
+
 void launch_clipped_sgd(float* p, const float* g, float* v, float* scratch,
                         float lr, float mu, float max_norm, long n, void* s) {
-  // scratch: kNPart partials + 1 scale
   hipStream_t st = (hipStream_t)s;
   sq_partials_k<<<kNPart, kBlock, 0, st>>>(g, nullptr, scratch, n);
   finalize_scale_k<<<1, kNPart, 0, st>>>(scratch, scratch + kNPart, kNPart,

@@ -17,6 +17,7 @@
 //                   so B is staged TRANSPOSED as [n][k] for contiguity:
 //                   B_lds[n][k = 0..31]
 #include "common.h"
+#include "launchers.h"
 #include <hip/hip_bf16.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -166,30 +167,10 @@ void gemm_bf16_k(const unsigned short* __restrict__ A,
     }
 }
 
-// f32 <-> bf16 casts (flat)
-__global__ void f32_to_bf16_k(const float* __restrict__ in,
-                              unsigned short* __restrict__ out, long n) {
-  long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride)
-    out[i] = f2bf_(in[i]);
-}
-
-__global__ void bf16_to_f32_k(const unsigned short* __restrict__ in,
-                              float* __restrict__ out, long n) {
-  long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride)
-    out[i] = bf2f_(in[i]);
-}
-
 extern "C" {
-void launch_splitk_reduce(const float* ws, float* C, const float* bias,
-                          int M, int N, int ldc, int SK, int relu, void* s);
-int gemm_f32_splitk(int M, int N, int K);
-
 // C is fp32 when c16 == nullptr, bf16 otherwise (split-K always reduces in
 // fp32 then the caller casts if needed — split-K path requires c16==null).
+// ws: gemm_splitk_ws_floats(M, N, SK) floats (gemm_f32.hip).
 void launch_gemm_bf16(const unsigned short* A, const unsigned short* B,
                       float* C, const float* bias, unsigned short* C16,
                       float* ws, int M, int N, int K, int lda, int ldb,
@@ -212,14 +193,5 @@ void launch_gemm_bf16(const unsigned short* A, const unsigned short* B,
                                              K, lda, ldb, ldc, k_per_chunk,
                                              relu, SK == 1);
   if (SK > 1) launch_splitk_reduce(ws, C, bias, M, N, ldc, SK, relu, s);
-}
-
-void launch_f32_to_bf16(const float* in, unsigned short* out, long n,
-                        void* s) {
-  f32_to_bf16_k<<<grid_for(n), kBlock, 0, (hipStream_t)s>>>(in, out, n);
-}
-void launch_bf16_to_f32(const unsigned short* in, float* out, long n,
-                        void* s) {
-  bf16_to_f32_k<<<grid_for(n), kBlock, 0, (hipStream_t)s>>>(in, out, n);
 }
 }

@@ -17,6 +17,7 @@
 // write fp32 partial slabs, a fixed-order reduce kernel (fused bias+relu)
 // combines them.  No atomics anywhere: bitwise run-to-run reproducible.
 #include "common.h"
+#include "launchers.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -398,7 +399,15 @@ int gemm_f32_splitk(int M, int N, int K) {
   return (int)(sk < 1 ? 1 : (sk > 192 ? 192 : sk));
 }
 
-// ws: null unless SK>1, then SK*M*N floats.
+// Split-K workspace of launch_gemm_f32 and launch_gemm_bf16 (both combine
+// through launch_splitk_reduce): SK slabs of M*N partials, then the
+// stage-1 slabs of a deep split.  No workspace for SK == 1.
+long gemm_splitk_ws_floats(int M, int N, int SK) {
+  if (SK == 1) return 0;
+  return (long)(SK + splitk_stage1_slabs(SK)) * M * N;
+}
+
+// ws: null unless SK>1, then gemm_splitk_ws_floats(M, N, SK) floats.
 // layout: 0 = NN, 1 = A transposed ([K][M]), 2 = B transposed ([N][K]).
 void launch_gemm_f32(const float* A, const float* B, float* C,
                      const float* bias, float* ws, int M, int N, int K,
@@ -449,11 +458,7 @@ void launch_gemm_f32(const float* A, const float* B, float* C,
     gemm_f32_k<false><<<grid, 256, 0, st>>>(A, B, out, bias, M, N, K, lda,
                                             ldb, ldc, k_per_chunk, relu,
                                             SK == 1);
-  if (SK > 1) {
-    extern void launch_splitk_reduce(const float*, float*, const float*,
-                                     int, int, int, int, int, void*);
-    launch_splitk_reduce(ws, C, bias, M, N, ldc, SK, relu, s);
-  }
+  if (SK > 1) launch_splitk_reduce(ws, C, bias, M, N, ldc, SK, relu, s);
 }
 
 // stage-1 partial for deep split-K: each (output, 16-slab chunk) gets its
@@ -482,16 +487,16 @@ __global__ void splitk_partial_k(const float* __restrict__ ws,
   }
 }
 
-// callers allocating a split-K workspace with SK > 16 must provide
-// ceil(SK/16) EXTRA slabs after the SK partials (stage-1 scratch)
+// ws holds gemm_splitk_ws_floats(M, N, SK) floats: the stage-1 scratch is
+// the splitk_stage1_slabs(SK) slabs after the SK partials
 void launch_splitk_reduce(const float* ws, float* C, const float* bias,
                           int M, int N, int ldc, int SK, int relu, void* s) {
   long n_out = (long)M * N;
-  if (SK > 16 && n_out <= 262144) {
-    int chunks = (SK + 15) / 16;
+  if (SK > kSplitKFold && n_out <= 262144) {
+    int chunks = splitk_stage1_slabs(SK);
     float* ws2 = const_cast<float*>(ws) + (long)SK * n_out;
     splitk_partial_k<<<grid_for(n_out * chunks), kBlock, 0,
-                       (hipStream_t)s>>>(ws, ws2, n_out, SK, 16);
+                       (hipStream_t)s>>>(ws, ws2, n_out, SK, kSplitKFold);
     splitk_reduce_k<<<grid_for(n_out), kBlock, 0, (hipStream_t)s>>>(
         ws2, C, bias, M, N, ldc, chunks, relu);
     return;

@@ -1,0 +1,297 @@
+// The launcher ABI: every function that crosses a translation-unit
+// boundary, declared once.  bindings.cpp (torch side) and every kernel
+// .hip include this, so the compiler checks each definition against the
+// declaration its callers see.  Plain C++: no HIP, no torch; streams are
+// void*, bf16 is raw unsigned short.  The *_ws_floats / *_scratch_floats /
+// *_ws_slabs functions are host arithmetic only: the size of the workspace
+// the launcher below them indexes.
+#pragma once
+#include <cstdint>
+
+extern "C" {
+// elementwise.hip
+void launch_relu_fwd(const float* x, float* y, long n, void* s);
+void launch_relu_bwd(const float* y, const float* dy, float* dx, long n,
+                     void* s);
+void launch_add_relu(const float* a, const float* b, float* y, long n,
+                     void* s);
+void launch_add_relu_bwd(float* a, const float* b, const float* y, long n,
+                         void* s);
+void launch_add_relu_bwd_bf16(unsigned short* a, const unsigned short* b,
+                              const unsigned short* y, long n, void* s);
+void launch_add_inplace(float* a, const float* b, long n, void* s);
+void launch_add_inplace_bf16(unsigned short* a, const unsigned short* b,
+                             long n, void* s);
+void launch_maxpool2x2_fwd(const float* x, float* y, uint8_t* idx, long B,
+                           int H, int W, int OH, int OW, int C, void* s);
+void launch_maxpool2x2_bwd(const float* dy, const uint8_t* idx, float* dx,
+                           long B, int H, int W, int OH, int OW, int C,
+                           void* s);
+void launch_maxpool2x2_bwd_relu(const float* dy, const uint8_t* idx,
+                                const float* relu_pooled, float* dx, long B,
+                                int H, int W, int OH, int OW, int C,
+                                void* s);
+void launch_maxpool2x2_fwd_bf16(const unsigned short* x, unsigned short* y,
+                                uint8_t* idx, long B, int H, int W, int OH,
+                                int OW, int C, void* s);
+void launch_maxpool2x2_bwd_bf16(const unsigned short* dy,
+                                const uint8_t* idx, unsigned short* dx,
+                                long B, int H, int W, int OH, int OW, int C,
+                                void* s);
+void launch_gap_fwd(const float* x, float* y, long B, int HW, int C,
+                    void* s);
+void launch_gap_bwd(const float* dy, float* dx, long B, int HW, int C,
+                    void* s);
+void launch_gap_bwd_relu(const float* dy, const float* y, float* dx, long B,
+                         int HW, int C, void* s);
+void launch_dropout_fwd(const float* x, float* y, uint8_t* mask, long n,
+                        float p, uint64_t seed, uint64_t offset, void* s);
+void launch_dropout_fwd_dev(const float* x, float* y, uint8_t* mask, long n,
+                            float p, const unsigned long long* state,
+                            int site, void* s);
+void launch_dropout_bwd(const float* dy, const uint8_t* mask, float* dx,
+                        long n, float p, void* s);
+void launch_dropout_relu_bwd(const float* dy, const uint8_t* mask,
+                             const float* y, float* dx, long n, float p,
+                             void* s);
+void launch_ce_fwd(const float* logits, const long* labels, float* softmax,
+                   float* row_loss, float* loss_out, int B, int C, void* s);
+void launch_ce_bwd(const float* softmax, const long* labels,
+                   const float* dloss, float* dlogits, int B, int C,
+                   void* s);
+void launch_eval_update(const float* logits, const long* labels, float* conf,
+                        double* loss_sum, int B, int C, int num_classes,
+                        void* s);
+void launch_nhwc_flatten(const float* in, float* out, long B, int C, int H,
+                         int W, void* s);
+void launch_nhwc_unflatten(const float* in, float* out, long B, int C,
+                           int H, int W, void* s);
+// elementwise.hip, bf16
+void launch_relu_fwd_bf16(const unsigned short* x, unsigned short* y,
+                          long n, void* s);
+void launch_relu_bwd_bf16(const unsigned short* y, const unsigned short* dy,
+                          unsigned short* dx, long n, void* s);
+void launch_add_relu_bf16(const unsigned short* a, const unsigned short* b,
+                          unsigned short* y, long n, void* s);
+void launch_dropout_fwd_dev_bf16(const unsigned short* x, unsigned short* y,
+                                 uint8_t* mask, long n, float p,
+                                 const unsigned long long* state, int site,
+                                 void* s);
+void launch_dropout_bwd_bf16(const unsigned short* dy, const uint8_t* mask,
+                             unsigned short* dx, long n, float p, void* s);
+void launch_gap_fwd_bf16(const unsigned short* x, unsigned short* y, long B,
+                         int HW, int C, void* s);
+void launch_gap_bwd_bf16(const unsigned short* dy, unsigned short* dx,
+                         long B, int HW, int C, void* s);
+void launch_gap_bwd_relu_bf16(const unsigned short* dy,
+                              const unsigned short* y, unsigned short* dx,
+                              long B, int HW, int C, void* s);
+void launch_nhwc_flatten_bf16(const unsigned short* in, unsigned short* out,
+                              long B, int C, int H, int W, void* s);
+void launch_nhwc_unflatten_bf16(const unsigned short* in,
+                                unsigned short* out, long B, int C, int H,
+                                int W, void* s);
+// flatopt.hip
+long flat_norm_scratch_floats();
+void launch_clipped_sgd(float* p, const float* g, float* v, float* scratch,
+                        float lr, float mu, float max_norm, long n, void* s);
+void launch_pgd_project(float* p, const float* t0, float* scratch, float clip,
+                        long n, void* s);
+void launch_delta64(const float* p, const double* t0, double* out, long n,
+                    void* s);
+void launch_gather_grads(const float* const* srcs, const long* offs,
+                         const long* lens, int count, float* flat, void* s);
+// aggregation.hip
+void launch_fused_avg_rlr_apply(const double* U, const double* w, int K,
+                                long n, double inv_wsum, int mode_rlr,
+                                double thresh, double slr, float* params,
+                                double* lr_out, double noise_std,
+                                uint64_t seed, uint64_t offset, void* s);
+void launch_rlr_vote(const double* U, int K, long n, double thresh,
+                     double slr, double* lr, void* s);
+void launch_agg_avg(const double* U, const double* w, int K, long n,
+                    double inv_wsum, double* out, void* s);
+void launch_agg_sign(const double* U, int K, long n, double* out, void* s);
+void launch_agg_comed(const double* U, int K, long n, double* out, void* s);
+void launch_apply_update(float* params, const double* agg, const double* lr,
+                         double slr, long n, void* s);
+void launch_add_noise(double* agg, double std, long n, uint64_t seed,
+                      uint64_t offset, void* s);
+// orderstat.hip (lr_out is nullable)
+int orderstat_max_k();
+void launch_agg_orderstat(const double* U, int K, long n, int lo, int hi,
+                          double inv_cnt, double* out, double* lr_out,
+                          double thresh, double slr, void* s);
+void launch_orderstat_rlr_apply(const double* U, int K, long n, int lo,
+                                int hi, double inv_cnt, int mode_rlr,
+                                double thresh, double slr, float* params,
+                                double* lr_out, void* s);
+// gemm_f32.hip
+int gemm_f32_splitk(int M, int N, int K);
+long gemm_splitk_ws_floats(int M, int N, int SK);
+void launch_gemm_f32(const float* A, const float* B, float* C,
+                     const float* bias, float* ws, int M, int N, int K,
+                     int lda, int ldb, int ldc, int SK, int relu,
+                     int layout, void* s);
+void launch_colsum(const float* dY, float* db, int M, int N, void* s);
+// gemm_bf16.hip
+void launch_gemm_bf16(const unsigned short* A, const unsigned short* B,
+                      float* C, const float* bias, unsigned short* C16,
+                      float* ws, int M, int N, int K, int lda, int ldb,
+                      int ldc, int SK, int relu, void* s);
+// conv_f32.hip
+void launch_conv_fwd(const float* x, const float* wt, const float* bias,
+                     float* y, int Nb, int C, int H, int W, int Kout, int R,
+                     int S, int OH, int OW, int stride, int pad, int relu,
+                     void* s);
+void launch_conv_bwd_data_relu(const float* dy, const float* wp,
+                               float* dx, const float* relu_y, int Nb,
+                               int C, int H, int W, int Kout, int R, int S,
+                               int OH, int OW, int stride, int pad,
+                               void* s);
+void launch_conv_bwd_data(const float* dy, const float* wp, float* dx,
+                          int Nb, int C, int H, int W, int Kout, int R,
+                          int S, int OH, int OW, int stride, int pad,
+                          void* s);
+int conv_bwd_weight_splitk(int Kout, int Ncrs, long Kdim);
+long conv_bwd_weight_ws_floats(int Kout, int Ncrs, int SK);
+void launch_conv_bwd_weight(const float* dy, const float* x, float* dw,
+                            float* ws, int SK, int Nb, int C, int H, int W,
+                            int Kout, int R, int S, int OH, int OW,
+                            int stride, int pad, void* s);
+int conv_db_chunks(long M, int Kout);
+long conv_db_ws_floats(int Kout);
+void launch_conv_db(const float* dy, float* db, float* partials, int Nb,
+                    int Kout, int OHW, void* s);
+long conv_dwperm_ws_floats(int Kout, int Ncrs, int SK);
+void launch_wperm_crs_ko(const float* w, float* out, int Kout, int C, int RS,
+                         void* s);
+void launch_wperm_kors_c(const float* w, float* out, int Kout, int C, int RS,
+                         void* s);
+// conv_bf16.hip
+int conv_bwd_weight_bf16_splitk(int Kout, int Ncrs, long Kdim);
+void launch_conv_fwd_bf16(const unsigned short* x, const unsigned short* wt,
+                          const float* bias, unsigned short* y, int Nb,
+                          int C, int H, int W, int Kout, int R, int S,
+                          int OH, int OW, int stride, int pad, int relu,
+                          void* s);
+void launch_conv_bwd_data_bf16_relu(const unsigned short* dy,
+                                    const unsigned short* wp,
+                                    unsigned short* dx,
+                                    const unsigned short* relu_y, int Nb,
+                                    int C, int H, int W, int Kout, int R,
+                                    int S, int OH, int OW, int stride,
+                                    int pad, void* s);
+void launch_conv_bwd_data_bf16(const unsigned short* dy,
+                               const unsigned short* wp, unsigned short* dx,
+                               int Nb, int C, int H, int W, int Kout, int R,
+                               int S, int OH, int OW, int stride, int pad,
+                               void* s);
+void launch_conv_bwd_weight_bf16(const unsigned short* dy,
+                                 const unsigned short* x, float* dw,
+                                 float* ws, int SK, int Nb, int C, int H,
+                                 int W, int Kout, int R, int S, int OH,
+                                 int OW, int stride, int pad, void* s);
+void launch_wperm_rsc_ko_bf16(const float* w, unsigned short* out, int Kout,
+                              int C, int RS, void* s);
+void launch_wperm_rsko_c_bf16(const float* w, unsigned short* out, int Kout,
+                              int C, int RS, void* s);
+void launch_conv_db_bf16(const unsigned short* dy, float* db,
+                         float* partials, int Nb, int Kout, int OHW,
+                         void* s);
+// conv_bwdw_tap.hip
+int conv_bwdw_tap_ok(int C, int H, int W, int Kout, int R, int S,
+                     int stride, int pad);
+int conv_bwdw_tap_s2_ok(int C, int H, int W, int Kout, int R, int S,
+                        int stride, int pad);
+int conv_bwdw_tap_ws_slabs(int Nb, int C, int Kout, int* S_out, int* G_out,
+                           int* chunks_out);
+void launch_conv_bwdw_tap_bf16(const unsigned short* dy,
+                               const unsigned short* x, float* dw,
+                               float* ws, int Nb, int C, int H, int W,
+                               int Kout, void* st);
+void launch_conv_bwdw_tap_s2_bf16(const unsigned short* dy,
+                                  const unsigned short* x, float* dw,
+                                  float* ws, int Nb, int C, int H, int W,
+                                  int Kout, void* st);
+int conv_tap_fwd_ok(int Cin, int H, int W, int Cout, int R, int S,
+                    int stride, int pad);
+void launch_conv_tap_fwd_bf16(const unsigned short* x,
+                              const unsigned short* wt, const float* bias,
+                              unsigned short* y,
+                              const unsigned short* relu_y, int Nb,
+                              int Cin, int H, int W, int Cout, int relu,
+                              int flip, void* st);
+int conv_tap_fwd_w4_ok(int Cin, int H, int W, int Cout, int R, int S,
+                       int stride, int pad);
+void launch_conv_tap_fwd_w4_bf16(const unsigned short* x,
+                                 const unsigned short* wt,
+                                 const float* bias, unsigned short* y,
+                                 const unsigned short* relu_y, int Nb,
+                                 int Cin, int Cout, int relu, int flip,
+                                 void* st);
+int conv_tap_bwdd_s2_ok(int C, int H, int W, int KO, int R, int S,
+                        int stride, int pad);
+void launch_conv_tap_bwdd_s2_bf16(const unsigned short* dy,
+                                  const unsigned short* wp,
+                                  unsigned short* dx,
+                                  const unsigned short* relu_y, int Nb,
+                                  int KO, int H, int W, int C, void* st);
+// batchnorm.hip
+int bn_scratch_floats(int C);
+void launch_bn_fwd(const float* x, const float* w, const float* b,
+                   float* running_mean, float* running_var, float* save_mean,
+                   float* save_rstd, float* y, float* scratch, int Nb,
+                   int C, int HW, float momentum, float eps, int training,
+                   int relu, void* s);
+void launch_bn_fwd_bf16(const unsigned short* x, const float* w,
+                        const float* b, float* running_mean,
+                        float* running_var, float* save_mean,
+                        float* save_rstd, unsigned short* y, float* scratch,
+                        int Nb, int C, int HW, float momentum, float eps,
+                        int training, int relu, void* s);
+void launch_bn_bwd(const float* x, const float* dy, const float* w,
+                   const float* save_mean, const float* save_rstd,
+                   float* scratch, float* dx, float* dw, float* db, int Nb,
+                   int C, int HW, int training, void* s);
+void launch_bn_bwd_bf16(const unsigned short* x, const unsigned short* dy,
+                        const float* w, const float* save_mean,
+                        const float* save_rstd, float* scratch,
+                        unsigned short* dx, float* dw, float* db, int Nb,
+                        int C, int HW, int training, void* s);
+// poison.hip
+void launch_poison_set_u8(uint8_t* data, const long* idxs, int B,
+                          const int* coords, int P, int H, int W, int C,
+                          int value, void* s);
+void launch_poison_set_f32(float* data, const long* idxs, int B,
+                           const int* coords, int P, int H, int W,
+                           float value, void* s);
+void launch_poison_addwrap_u8(uint8_t* data, const long* idxs, int B,
+                              const uint8_t* mask, int HW, void* s);
+void launch_poison_subf(float* data, const long* idxs, int B,
+                        const uint8_t* mask, int HW, void* s);
+void launch_normalize_u8(const uint8_t* raw, float* out, long B, int H,
+                         int W, int C, const float* mean, const float* stdv,
+                         void* s);
+
+// ---- internal: helpers shared between sibling kernel files only ----
+// gemm_f32.hip
+void launch_splitk_reduce(const float* ws, float* C, const float* bias,
+                          int M, int N, int ldc, int SK, int relu, void* s);
+void launch_splitk_partial(const float* ws, float* out, long n_out, int S,
+                           int zstride, void* s);
+// conv_f32.hip
+void launch_splitk_reduce_dwperm(const float* ws, float* dw, int Kout,
+                                 int C, int RS, int SK, void* s);
+void launch_dwperm_rsc_crs(const float* in, float* out, int Kout, int C,
+                           int RS, void* s);
+void launch_conv_db_stage2(const float* partials, float* db, int Kout,
+                           int chunks, void* s);
+// conv_bf16.hip (the variant sweep of tests/perf/bwdw_micro.hip)
+void launch_conv_bwd_weight_bf16_ex(const unsigned short* dy,
+                                    const unsigned short* x, float* dw,
+                                    float* ws, int SK, int variant, int Nb,
+                                    int C, int H, int W, int Kout, int R,
+                                    int S, int OH, int OW, int stride,
+                                    int pad, void* s);
+}

@@ -34,6 +34,7 @@
 // the rows it loads, the L partial counts meet in LDS.  Sums of +-1 are
 // exact in any order, so lr is bitwise rlr_vote_k's.
 #include "common.h"
+#include "launchers.h"
 
 constexpr int kTile = 32;             // columns per block tile (256 B rows)
 constexpr int kOrderstatMaxK = 512;   // P*kTile*8 B = 128 KiB of 160 KiB LDS

@@ -5,6 +5,7 @@
 // normalized on device — poisoned/clean batches never leave HBM
 // (BASELINE.json requirement).
 #include "common.h"
+#include "launchers.h"
 
 // ---- set coords: raw (B,H,W) u8 | (B,H,W,C) u8 | (B,1,H,W) f32 ----
 // idxs: which images of the full dataset to poison.

@@ -15,17 +15,7 @@
 #include <cmath>
 #include <vector>
 
-extern "C" {
-void launch_conv_bwd_weight_bf16_ex(const unsigned short*,
-                                    const unsigned short*, float*, float*,
-                                    int, int, int, int, int, int, int, int,
-                                    int, int, int, int, int, void*);
-int conv_bwd_weight_bf16_splitk(int, int, long);
-void launch_conv_bwd_weight(const float*, const float*, float*, float*,
-                            int, int, int, int, int, int, int, int, int,
-                            int, int, int, void*);
-int conv_bwd_weight_splitk(int, int, long);
-}
+#include "../../rlr_amd/ops/csrc/launchers.h"
 
 #define CHK(x)                                                      \
   do {                                                              \
@@ -77,7 +67,8 @@ static void f32_sweep(int iters) {
     for (int si = 0; si < 5; ++si) {
       int SK = sks[si];
       if (si > 0 && SK == skp) continue;
-      if ((long)(SK + 1) * sh.K * Ncrs * 4 > 800L * 1024 * 1024) continue;
+      if (conv_bwd_weight_ws_floats(sh.K, Ncrs, SK) * 4 > 800L * 1024 * 1024)
+        continue;
       for (int w = 0; w < 3; ++w)
         launch_conv_bwd_weight(ddy, dx, dw, ws, SK, sh.Nb, sh.C, sh.H,
                                sh.W, sh.K, sh.R, sh.S, OH, OW, sh.stride,
@@ -147,8 +138,9 @@ int main(int argc, char** argv) {
         for (int j = 1; j < si; ++j) dup |= (sks[j] == SK);
         if (si > 0 && SK == skp) dup = true;
         if (dup && si > 0) continue;
-        // slab bound: SK*K*Ncrs floats must fit ws
-        if ((long)(SK + 1) * sh.K * Ncrs * 4 > 600L * 1024 * 1024) continue;
+        // the slabs the launcher touches must fit ws
+        if (conv_dwperm_ws_floats(sh.K, Ncrs, SK) * 4 > 600L * 1024 * 1024)
+          continue;
         float* out = variant == 0 ? dw0 : dw1;
         for (int w = 0; w < 3; ++w)
           launch_conv_bwd_weight_bf16_ex(ddy, dx, out, ws, SK, variant,
