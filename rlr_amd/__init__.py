@@ -8,7 +8,8 @@ attacks, with FedAvg / coordinate-median / sign aggregation modulated by the
 per-parameter robust-learning-rate sign vote.  Build addition: the
 coordinate-wise trimmed mean (--aggr trmean, Yin et al. 2018), sharing one
 LDS sorting-network kernel family with the median at more than 64 sampled
-agents.
+agents, and Krum / Multi-Krum (--aggr krum, Blanchard et al. 2017) on an
+fp64 MFMA pairwise-distance kernel.
 
 Architecture (nothing here is a port):
   * one process per GPU; sampled agents are sharded contiguously across

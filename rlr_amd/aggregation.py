@@ -25,6 +25,23 @@ Rules (each a HIP kernel on the GPU path, ops/csrc/aggregation.hip):
     agent-order invariant and bitwise equal between CPU and GPU.
     Without noise, trmean (and comed above K = 64) take ONE fused kernel:
     LDS sort + sign vote from the resident tile + fp32 apply.
+  * Krum / Multi-Krum (build addition, --aggr krum; Blanchard et al.,
+    2017): the one agent-wise rule.  D[i][j] = ||U_i - U_j||^2 (K x K fp64,
+    exactly symmetric, zero diagonal, clamped at 0; on the GPU the fp64
+    MFMA Gram kernel ops/csrc/pairdist.hip, on the CPU direct differences).
+    With f = --krum_f agents assumed Byzantine and c = K - f - 2, score[i]
+    sorts row i of D ascending, skips element 0 (the diagonal zero) and
+    adds elements 1..c sequentially in ASCENDING order, times 1/c — exactly
+    agg_orderstat(D, 1, c + 1) on the symmetric D.  The m = --krum_m agents
+    with the lowest score are kept (stable sort: ties go to the lower
+    sampled position; m = 0 means K - f, Multi-Krum; m = 1 is classic
+    Krum) and averaged UNWEIGHTED like comed/trmean, accumulated in sampled
+    order as acc += s_k * U_k with s_k in {1.0, 0.0}, times 1/m — the fused
+    avg kernel with 0/1 weights is the same computation.  The RLR vote is
+    taken over ALL K sampled updates: Krum decides what is averaged, the
+    vote decides the direction.  Noise behaves as for avg on each backend.
+    BatchNorm buffers are averaged unweighted over the same selection.
+    Non-finite updates are out of scope (0 * inf is NaN).
   * sign (aggregation.py:71-75): sign(sum_k sign(U_k)).
   * optional N(0, noise*clip) gaussian noise (aggregation.py:34-35) from a
     per-round derived stream.  NOTE: the fused GPU avg path draws noise
@@ -57,6 +74,7 @@ class Aggregation:
         self.n_params = n_params
         self.poisoned_val_loader = poisoned_val_loader
         self.cum_net_mov = 0.0
+        self.last_selected = None   # krum: sampled positions kept last round
 
     # ------------------------------------------------------------- entry
 
@@ -71,11 +89,18 @@ class Aggregation:
             stacked = agent_updates
             assert agent_ids is not None
 
-        if _gpu(stacked) and self.args.aggr == 'avg':
+        krum = self.args.aggr == 'krum'
+        if krum:
+            self.last_selected = self.krum_select(stacked)
+            self._log_krum(agent_ids, cur_round)
+
+        if _gpu(stacked) and (self.args.aggr == 'avg' or krum):
             # headline path: ONE fused kernel does sign-vote + weighted avg
             # + noise + fp32 apply in a single pass over the K x n matrix
+            # (krum: 0/1 weights over the selection, vote over all K)
             from .utils.rng import derive_seed
-            w = self._weights(agent_ids, stacked.device)
+            w = (self._krum_weights(stacked.shape[0], stacked.device) if krum
+                 else self._weights(agent_ids, stacked.device))
             noise_std = (self.args.noise * self.args.clip
                          if self.args.noise > 0 else 0.0)
             seed = derive_seed(self.args.seed, 'noise', cur_round)
@@ -116,6 +141,8 @@ class Aggregation:
             agg = self.agg_trmean(stacked)
         elif self.args.aggr == 'sign':
             agg = self.agg_sign(stacked)
+        elif krum:
+            agg = self._krum_mean(stacked, self.last_selected)
         else:
             raise ValueError(self.args.aggr)
 
@@ -194,6 +221,94 @@ class Aggregation:
             out += kept[r]
         return out * (1.0 / (K - 2 * b))
 
+    # -------------------------------------------------------------- krum
+
+    def _krum_counts(self, K):
+        """(c, m): neighbours scored per agent and agents kept."""
+        f, m = self.args.krum_f, self.args.krum_m
+        if f < 0 or K - f - 2 < 1:
+            raise ValueError(
+                f"krum_f={f} leaves K - f - 2 = {K - f - 2} neighbours to "
+                f"score each of K={K} sampled agents by; need at least 1")
+        if m == 0:
+            m = K - f
+        if not 1 <= m <= K - f:
+            raise ValueError(
+                f"krum_m={m} must be in [1, K - krum_f] = [1, {K - f}] for "
+                f"K={K} sampled agents")
+        return K - f - 2, m
+
+    def pairwise_sqdist(self, stacked):
+        """D[i][j] = ||U_i - U_j||^2: exactly symmetric, zero diagonal,
+        no entry below 0."""
+        K = stacked.shape[0]
+        if _gpu(stacked):
+            if K <= ext().pairdist_max_k():
+                return ext().pairwise_sqdist(stacked)
+            # above the kernel's K limit: Gram form in torch, one triangle
+            # mirrored so the properties hold whatever the BLAS does
+            G = stacked @ stacked.T
+            g = G.diagonal()
+            D = (g.unsqueeze(1) + g.unsqueeze(0) - 2.0 * G).clamp_(min=0.0)
+            D = torch.triu(D, diagonal=1)
+            return D + D.T
+        D = torch.empty(K, K, dtype=torch.float64, device=stacked.device)
+        for i in range(K):
+            D[i] = ((stacked - stacked[i]) ** 2).sum(1)
+        D = torch.triu(D, diagonal=1)
+        return D + D.T
+
+    def krum_scores(self, D):
+        """score[i] = mean of the c smallest distances from agent i to the
+        others, summed in ascending order."""
+        K = D.shape[0]
+        c, _ = self._krum_counts(K)
+        if _gpu(D) and K <= ext().orderstat_max_k():
+            # D is symmetric: sorting its columns sorts its rows
+            return ext().agg_orderstat(D.contiguous(), 1, c + 1, False,
+                                       0.0, 0.0)[0]
+        srt = torch.sort(D, dim=0).values
+        out = torch.zeros(K, dtype=torch.float64, device=D.device)
+        for r in range(1, c + 1):
+            out += srt[r]
+        return out * (1.0 / c)
+
+    def krum_select(self, stacked):
+        """Sampled positions of the m lowest-score agents, ascending."""
+        _, m = self._krum_counts(stacked.shape[0])
+        scores = self.krum_scores(self.pairwise_sqdist(stacked))
+        order = torch.sort(scores, stable=True).indices
+        return torch.sort(order[:m]).values
+
+    def _krum_weights(self, K, device):
+        w = torch.zeros(K, dtype=torch.float64, device=device)
+        w[self.last_selected.to(device)] = 1.0
+        return w
+
+    def _krum_mean(self, stacked, selected):
+        K = stacked.shape[0]
+        s = torch.zeros(K, dtype=torch.float64, device=stacked.device)
+        s[selected] = 1.0
+        if _gpu(stacked):
+            return ext().agg_avg(stacked, s)
+        out = torch.zeros(stacked.shape[1], dtype=torch.float64,
+                          device=stacked.device)
+        for k in range(K):
+            out += s[k] * stacked[k]
+        return out * (1.0 / selected.numel())
+
+    def agg_krum(self, stacked):
+        """Unweighted mean of the Krum-selected updates (module docstring).
+        Remembers the selection in last_selected."""
+        self.last_selected = self.krum_select(stacked)
+        return self._krum_mean(stacked, self.last_selected)
+
+    def _log_krum(self, agent_ids, cur_round):
+        if self.writer:
+            n_bad = sum(1 for p in self.last_selected.tolist()
+                        if agent_ids[p] < self.args.num_corrupt)
+            self.writer.add_scalar('Krum/Corrupt_Selected', n_bad, cur_round)
+
     def agg_sign(self, stacked):
         if _gpu(stacked):
             return ext().agg_sign(stacked)
@@ -222,14 +337,18 @@ class Aggregation:
 
     def aggregate_buffers(self, global_model, buffer_deltas, agent_ids):
         """FedAvg-BN: data-weighted mean of BatchNorm running-stat deltas
-        (build extension — the reference has no BN)."""
+        (build extension — the reference has no BN).  Under krum: the
+        unweighted mean over the agents selected for the parameters."""
         if global_model.n_buffers == 0 or buffer_deltas is None:
             return
         if isinstance(buffer_deltas, (list, tuple)) and not buffer_deltas:
             return
-        w = self._weights(agent_ids, buffer_deltas.device
-                          if isinstance(buffer_deltas, torch.Tensor)
-                          else buffer_deltas[0].device)
+        dev = (buffer_deltas.device if isinstance(buffer_deltas, torch.Tensor)
+               else buffer_deltas[0].device)
+        if self.args.aggr == 'krum':
+            w = self._krum_weights(len(agent_ids), dev)
+        else:
+            w = self._weights(agent_ids, dev)
         if isinstance(buffer_deltas, list):
             buffer_deltas = torch.stack(buffer_deltas)
         if _gpu(buffer_deltas):

@@ -523,6 +523,27 @@ torch::Tensor orderstat_rlr_apply(torch::Tensor U, int64_t lo, int64_t hi,
   return lr;
 }
 
+// (K, n) fp64, contiguous, on device, 1 <= K <= pairdist_max_k(), n >= 1.
+static void check_pairdist(const torch::Tensor& U) {
+  CHK(U.is_cuda());
+  CHK(U.dim() == 2);
+  CHK(U.scalar_type() == torch::kFloat64);
+  CHK(U.is_contiguous());
+  CHK(U.size(0) >= 1 && U.size(0) <= pairdist_max_k());
+  CHK(U.size(1) >= 1);
+}
+
+torch::Tensor pairwise_sqdist(torch::Tensor U) {
+  check_pairdist(U);
+  int K = U.size(0);
+  long n = U.size(1);
+  auto ws = torch::empty({pairdist_ws_doubles(K, n)}, U.options());
+  auto D = torch::empty({K, K}, U.options());
+  launch_pairwise_sqdist(U.data_ptr<double>(), K, n, ws.data_ptr<double>(),
+                         D.data_ptr<double>(), stream_of(U));
+  return D;
+}
+
 void apply_update(torch::Tensor params, torch::Tensor agg, torch::Tensor lr,
                   double slr) {
   CHK_CUDA(params);
@@ -1032,6 +1053,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("agg_orderstat", &agg_orderstat);
   m.def("orderstat_rlr_apply", &orderstat_rlr_apply);
   m.def("orderstat_max_k", &orderstat_max_k);
+  m.def("pairwise_sqdist", &pairwise_sqdist);
+  m.def("pairdist_max_k", &pairdist_max_k);
+  m.def("pairdist_chunks", &pairdist_chunks);
+  m.def("pairdist_ws_doubles", &pairdist_ws_doubles);
   m.def("add_noise", &add_noise);
   m.def("gemm", &gemm);
   m.def("gemm_bf16", &gemm_bf16);

@@ -3,8 +3,8 @@
 // .hip include this, so the compiler checks each definition against the
 // declaration its callers see.  Plain C++: no HIP, no torch; streams are
 // void*, bf16 is raw unsigned short.  The *_ws_floats / *_scratch_floats /
-// *_ws_slabs functions are host arithmetic only: the size of the workspace
-// the launcher below them indexes.
+// *_ws_slabs / *_ws_doubles functions are host arithmetic only: the size of
+// the workspace the launcher below them indexes.
 #pragma once
 #include <cstdint>
 
@@ -126,6 +126,18 @@ void launch_orderstat_rlr_apply(const double* U, int K, long n, int lo,
                                 int hi, double inv_cnt, int mode_rlr,
                                 double thresh, double slr, float* params,
                                 double* lr_out, void* s);
+// pairdist.hip: D (K, K) = squared L2 distances between the rows of U
+// (K, n), 1 <= K <= pairdist_max_k().  Stage 1 splits n into
+// pairdist_chunks(K, n) chunks (a pure function of K and n) and writes one
+// 64 x 64 slab per (chunk, upper-triangle pair of 64-row tiles) to ws, or
+// one 16 x 16 slab per chunk when K <= 16, and the reduced slabs behind
+// them; chunks * pairs <= 1024 and pairs <= 36, so ws is at most 1060 slabs
+// of 32 KiB < 34 MiB (bound: <= 64 MiB) for every K <= 512 and every n.
+int pairdist_max_k();
+int pairdist_chunks(int K, long n);
+long pairdist_ws_doubles(int K, long n);
+void launch_pairwise_sqdist(const double* U, int K, long n, double* ws,
+                            double* D, void* s);
 // gemm_f32.hip
 int gemm_f32_splitk(int M, int N, int K);
 long gemm_splitk_ws_floats(int M, int N, int SK);

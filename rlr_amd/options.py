@@ -28,8 +28,9 @@ def args_parser(argv=None):
     parser.add_argument('--rounds', type=int, default=200,
                         help="number of communication rounds R")
     parser.add_argument('--aggr', type=str, default='avg',
-                        choices=['avg', 'comed', 'sign', 'trmean'],
-                        help="aggregation rule (trmean is a build addition)")
+                        choices=['avg', 'comed', 'sign', 'trmean', 'krum'],
+                        help="aggregation rule (trmean and krum are build "
+                             "additions)")
     parser.add_argument('--local_ep', type=int, default=2,
                         help="number of local epochs E")
     parser.add_argument('--bs', type=int, default=256,
@@ -68,6 +69,12 @@ def args_parser(argv=None):
     parser.add_argument('--trim_frac', type=float, default=0.1,
                         help="fraction of sampled agents trimmed from each "
                              "end per coordinate (--aggr trmean)")
+    parser.add_argument('--krum_f', type=int, default=1,
+                        help="number of sampled agents assumed Byzantine "
+                             "(--aggr krum)")
+    parser.add_argument('--krum_m', type=int, default=0,
+                        help="number of agents Krum keeps: 1 = classic Krum, "
+                             "0 = K - krum_f (Multi-Krum)")
     parser.add_argument('--seed', type=int, default=42,
                         help="master seed; all RNG streams derive from it "
                              "world-size-invariantly")
@@ -109,11 +116,17 @@ def args_parser(argv=None):
 def finalize_args(args):
     """Derived rules. server_lr forced to 1 unless aggr=='sign'
     (reference federated.py:23); 0 <= trim_frac < 0.5 so that at least one
-    value per coordinate survives the trim for every K."""
+    value per coordinate survives the trim for every K; krum_f, krum_m >= 0
+    (their upper limits depend on the sampled K and are checked by the
+    server)."""
     args.server_lr = args.server_lr if args.aggr == 'sign' else 1.0
     if not 0 <= args.trim_frac < 0.5:
         raise ValueError(
             f"--trim_frac must be in [0, 0.5), got {args.trim_frac}")
+    if args.krum_f < 0 or args.krum_m < 0:
+        raise ValueError(
+            f"--krum_f and --krum_m must be >= 0, got {args.krum_f} and "
+            f"{args.krum_m}")
     if args.device is None:
         import torch
         if torch.cuda.is_available():

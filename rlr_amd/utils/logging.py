@@ -7,15 +7,17 @@ from time import ctime
 
 
 def run_name(args):
-    """Reference federated.py:27-30 run-name string; the trimmed mean (a
-    build addition) appends its trim fraction, every other rule keeps the
-    reference name byte for byte."""
+    """Reference federated.py:27-30 run-name string; the trimmed mean and
+    krum (build additions) append their own flags, every other rule keeps
+    the reference name byte for byte."""
     name = (f"time:{ctime()}-clip_val:{args.clip}-noise_std:{args.noise}"
             f"-aggr:{args.aggr}-s_lr:{args.server_lr}-num_cor:{args.num_corrupt}"
             f"thrs_robustLR:{args.robustLR_threshold}"
             f"-num_corrupt:{args.num_corrupt}-pttrn:{args.pattern_type}")
     if args.aggr == 'trmean':
         name += f"-trim:{args.trim_frac}"
+    if args.aggr == 'krum':
+        name += f"-krum_f:{args.krum_f}-krum_m:{args.krum_m}"
     return name
 
 
@@ -37,6 +39,8 @@ def print_exp_details(args):
     print(f'    Aggregation Function: {args.aggr}')
     if args.aggr == 'trmean':
         print(f'    Trim Fraction: {args.trim_frac}')
+    if args.aggr == 'krum':
+        print(f'    Krum f / m: {args.krum_f} / {args.krum_m}')
     print(f'    Number of agents: {args.num_agents}')
     print(f'    Fraction of agents: {args.agent_frac}')
     print(f'    Batch size: {args.bs}')
