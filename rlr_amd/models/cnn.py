@@ -67,13 +67,9 @@ class CNN_MNIST(_OpsModel):
         st = self.rng.gpu_state(x.device)
         a1 = E.conv2d_fwd(x, self.conv1.weight, self.conv1.bias, 1, 0, True)
         a2 = E.conv2d_fwd(a1, self.conv2.weight, self.conv2.bias, 1, 0, True)
-        pl, idx = E.maxpool2x2_fwd(a2)
-        fl = E.nhwc_flatten(pl)
-        d1, m1 = E.dropout_fwd_dev(fl, p, st, 0)
+        # pool + flatten + dropout-1 in one kernel (ops/csrc/fused_tail.hip)
+        pl, idx, d1, m1 = E.pool_flatten_dropout_fwd(a2, p, st, 0)
         h1 = E.linear_fwd(d1, self.fc1.weight, self.fc1.bias, True)
-        d2, m2 = E.dropout_fwd_dev(h1, p, st, 1)
-        out = E.linear_fwd(d2, self.fc2.weight, self.fc2.bias, False)
-        loss, softmax = E.cross_entropy_fwd(out, labels)
 
         # Backward with the relu masks FUSED away (each bitwise-identical
         # to the separate relu_bwd: see maxpool2x2_bwd_gather4_k /
@@ -82,15 +78,15 @@ class CNN_MNIST(_OpsModel):
         #   * conv2's relu folds into the maxpool gather via the pooled
         #     values (window max == pooled value for post-relu inputs);
         #   * conv1's relu folds into conv2's bwd-data epilogue.
-        g = E.cross_entropy_bwd(softmax, labels, dloss)
-        g = E.linear_bwd_into(d2, self.fc2.weight, g,
-                              self.fc2.weight.grad, self.fc2.bias.grad, True)
-        g = E.dropout_relu_bwd(g, m2, h1, p)
+        # The classifier head (dropout-2, fc2, CE, and their backwards up
+        # to fc1's relu mask) is two launches; the seam backward is one.
+        loss, g = E.fc_head_step(h1, self.fc2.weight, self.fc2.bias, labels,
+                                 dloss, p, st, 1, self.fc2.weight.grad,
+                                 self.fc2.bias.grad)
         g = E.linear_bwd_into(d1, self.fc1.weight, g,
                               self.fc1.weight.grad, self.fc1.bias.grad, True)
-        g = E.dropout_bwd(g, m1, p)
-        g = E.nhwc_unflatten(g, pl.shape[1], pl.shape[2], pl.shape[3])
-        g = E.maxpool2x2_bwd_relu(g, idx, pl, list(a2.shape))
+        g = E.dropout_unflatten_pool_bwd_relu(g, m1, idx, pl, p,
+                                              list(a2.shape))
         g = E.conv2d_bwd_into(a1, self.conv2.weight, g, 1, 0, True,
                               self.conv2.weight.grad, self.conv2.bias.grad,
                               a1)
@@ -140,31 +136,24 @@ class CNN_CIFAR(_OpsModel):
         a2 = E.conv2d_fwd(p1, self.conv2.weight, self.conv2.bias, 1, 0, True)
         p2, i2 = E.maxpool2x2_fwd(a2)
         a3 = E.conv2d_fwd(p2, self.conv3.weight, self.conv3.bias, 1, 0, True)
-        p3, i3 = E.maxpool2x2_fwd(a3)
-        fl = E.nhwc_flatten(p3)
-        d1, m1 = E.dropout_fwd_dev(fl, p, st, 0)
+        p3, i3, d1, m1 = E.pool_flatten_dropout_fwd(a3, p, st, 0)
         h1 = E.linear_fwd(d1, self.fc1.weight, self.fc1.bias, True)
         d2, m2 = E.dropout_fwd_dev(h1, p, st, 1)
         h2 = E.linear_fwd(d2, self.fc2.weight, self.fc2.bias, True)
-        d3, m3 = E.dropout_fwd_dev(h2, p, st, 2)
-        out = E.linear_fwd(d3, self.fc3.weight, self.fc3.bias, False)
-        loss, softmax = E.cross_entropy_fwd(out, labels)
 
         # relu masks fused (see CNN_MNIST.manual_step): fc relus fold
         # into the dropout backwards; every conv relu folds into the
         # following maxpool gather via the pooled values.
-        g = E.cross_entropy_bwd(softmax, labels, dloss)
-        g = E.linear_bwd_into(d3, self.fc3.weight, g,
-                              self.fc3.weight.grad, self.fc3.bias.grad, True)
-        g = E.dropout_relu_bwd(g, m3, h2, p)
+        loss, g = E.fc_head_step(h2, self.fc3.weight, self.fc3.bias, labels,
+                                 dloss, p, st, 2, self.fc3.weight.grad,
+                                 self.fc3.bias.grad)
         g = E.linear_bwd_into(d2, self.fc2.weight, g,
                               self.fc2.weight.grad, self.fc2.bias.grad, True)
         g = E.dropout_relu_bwd(g, m2, h1, p)
         g = E.linear_bwd_into(d1, self.fc1.weight, g,
                               self.fc1.weight.grad, self.fc1.bias.grad, True)
-        g = E.dropout_bwd(g, m1, p)
-        g = E.nhwc_unflatten(g, p3.shape[1], p3.shape[2], p3.shape[3])
-        g = E.maxpool2x2_bwd_relu(g, i3, p3, list(a3.shape))
+        g = E.dropout_unflatten_pool_bwd_relu(g, m1, i3, p3, p,
+                                              list(a3.shape))
         g = E.conv2d_bwd_into(p2, self.conv3.weight, g, 1, 0, True,
                               self.conv3.weight.grad, self.conv3.bias.grad,
                               None)

@@ -680,6 +680,113 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> linear_bwd(
   return {dx, dw, db};
 }
 
+// ------------------------------------------------------------ fused tail
+// (manual tape, fp32; see fused_tail.hip).  Each binding runs the unfused
+// sequence it replaces when its predicate is false, so the result never
+// depends on which path ran.
+
+static const unsigned long long* dropout_state(const torch::Tensor& state) {
+  CHK(state.scalar_type() == torch::kUInt64 ||
+      state.scalar_type() == torch::kInt64);
+  return (const unsigned long long*)state.data_ptr();
+}
+
+// maxpool2x2 + flatten (CHW order) + dropout of a channels_last a:
+// -> (pooled, idx, d, mask)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
+pool_flatten_dropout_fwd(torch::Tensor a, double p, torch::Tensor state,
+                         int64_t site) {
+  TORCH_CHECK(a.is_cuda() && a.dim() == 4 && !is_bf16(a));
+  int Nb = a.size(0), C = a.size(1), H = a.size(2), W = a.size(3);
+  if (!pool_seam_fused_ok(C, H, W)) {
+    auto [pooled, idx] = maxpool2x2_fwd(a);
+    auto [d, mask] = dropout_fwd_dev(nhwc_flatten(pooled), p, state, site);
+    return {pooled, idx, d, mask};
+  }
+  a = cl(a, "seam_fwd.a");
+  int OH = H / 2, OW = W / 2;
+  auto pooled = empty_cl({Nb, C, OH, OW}, a.options());
+  auto idx = empty_cl({Nb, C, OH, OW}, a.options().dtype(torch::kUInt8));
+  auto d = torch::empty({Nb, (int64_t)C * OH * OW}, a.options());
+  auto mask = torch::empty({Nb, (int64_t)C * OH * OW},
+                           a.options().dtype(torch::kUInt8));
+  launch_pool_flatten_dropout_fwd(
+      a.data_ptr<float>(), pooled.data_ptr<float>(), idx.data_ptr<uint8_t>(),
+      d.data_ptr<float>(), mask.data_ptr<uint8_t>(), Nb, H, W, C, (float)p,
+      dropout_state(state), (int)site, stream_of(a));
+  return {pooled, idx, d, mask};
+}
+
+// dropout backward + unflatten + maxpool backward with the relu mask of
+// the pooled values: g (B, C*OH*OW) -> dx, channels_last of x_shape
+torch::Tensor dropout_unflatten_pool_bwd_relu(torch::Tensor g,
+                                              torch::Tensor mask,
+                                              torch::Tensor idx,
+                                              torch::Tensor pooled, double p,
+                                              std::vector<int64_t> x_shape) {
+  TORCH_CHECK(g.is_cuda() && !is_bf16(g) && x_shape.size() == 4);
+  int Nb = x_shape[0], C = x_shape[1], H = x_shape[2], W = x_shape[3];
+  int OH = pooled.size(2), OW = pooled.size(3);
+  TORCH_CHECK(OH == H / 2 && OW == W / 2 && pooled.size(1) == C &&
+              g.numel() == (int64_t)Nb * C * OH * OW &&
+              mask.numel() == g.numel() && idx.numel() == g.numel());
+  if (!pool_seam_fused_ok(C, H, W)) {
+    auto gu = nhwc_unflatten(dropout_bwd(g, mask, p), C, OH, OW);
+    if ((C % 4) == 0) return maxpool2x2_bwd_relu(gu, idx, pooled, x_shape);
+    // the relu-mask gather needs C % 4 == 0: mask through the pooled values
+    // first (a select either way, so the order does not matter bitwise)
+    return maxpool2x2_bwd(relu_bwd(pooled, gu), idx, x_shape);
+  }
+  g = g.contiguous();
+  mask = mask.contiguous();
+  idx = cl(idx, "seam_bwd.idx");
+  pooled = cl(pooled, "seam_bwd.pooled");
+  auto dx = empty_cl({Nb, C, H, W}, g.options());
+  launch_dropout_unflatten_pool_bwd_relu(
+      g.data_ptr<float>(), mask.data_ptr<uint8_t>(), idx.data_ptr<uint8_t>(),
+      pooled.data_ptr<float>(), dx.data_ptr<float>(), Nb, H, W, C, (float)p,
+      stream_of(g));
+  return dx;
+}
+
+// The classifier head of a step: dropout(h1) -> fc -> mean CE, and back to
+// the gradient of h1 (pre-dropout, relu-masked).  dw / db are written into
+// the caller's flat-grad views.  -> (loss, g_h1)
+std::tuple<torch::Tensor, torch::Tensor> fc_head_step(
+    torch::Tensor h1, torch::Tensor w, torch::Tensor b, torch::Tensor labels,
+    torch::Tensor dloss, double p, torch::Tensor state, int64_t site,
+    torch::Tensor dw_out, torch::Tensor db_out) {
+  TORCH_CHECK(h1.is_cuda() && h1.dim() == 2 && !is_bf16(h1));
+  int B = h1.size(0), H = h1.size(1), C = w.size(0);
+  TORCH_CHECK(w.size(1) == H && b.numel() == C && labels.numel() == B);
+  TORCH_CHECK(dw_out.is_contiguous() && dw_out.numel() == (int64_t)C * H &&
+              db_out.is_contiguous() && db_out.numel() == C);
+  if (!fc_head_fused_ok(B, H, C)) {
+    auto [d2, m2] = dropout_fwd_dev(h1, p, state, site);
+    auto out = linear_fwd(d2, w, b, false);
+    auto [loss, softmax] = cross_entropy_fwd(out, labels);
+    auto g = cross_entropy_bwd(softmax, labels, dloss);
+    g = linear_bwd_into(d2, w, g, dw_out, db_out, true);
+    return {loss, dropout_relu_bwd(g, m2, h1, p)};
+  }
+  h1 = h1.contiguous();
+  w = w.contiguous();
+  b = b.contiguous();
+  labels = labels.contiguous();
+  auto dl = dloss.to(h1.device()).contiguous();
+  auto ws = torch::empty({fc_head_ws_floats(B, H, C)}, h1.options());
+  auto g_h1 = torch::empty_like(h1);
+  auto loss = torch::empty({}, h1.options());
+  launch_fc_head_step(h1.data_ptr<float>(), w.data_ptr<float>(),
+                      b.data_ptr<float>(), labels.data_ptr<int64_t>(),
+                      dl.data_ptr<float>(), ws.data_ptr<float>(),
+                      g_h1.data_ptr<float>(), dw_out.data_ptr<float>(),
+                      db_out.data_ptr<float>(), loss.data_ptr<float>(), B, H,
+                      C, (float)p, dropout_state(state), (int)site,
+                      stream_of(h1));
+  return {loss, g_h1};
+}
+
 // ------------------------------------------------------------------ conv
 
 torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w,
@@ -1114,6 +1221,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                                   int g, int h) {
     return conv_bwdw_tap_s2_ok(a, b, c, d, e, f, g, h) != 0;
   });
+  m.def("pool_flatten_dropout_fwd", &pool_flatten_dropout_fwd);
+  m.def("dropout_unflatten_pool_bwd_relu", &dropout_unflatten_pool_bwd_relu);
+  m.def("fc_head_step", &fc_head_step);
+  m.def("pool_seam_fused_ok", &pool_seam_fused_ok);
+  m.def("fc_head_fused_ok", &fc_head_fused_ok);
+  m.def("fc_head_ws_floats", &fc_head_ws_floats);
   m.def("add_", &add_inplace);
   m.def("add_relu_bwd_", &add_relu_bwd_);
   m.def("gap_bwd_relu", &gap_bwd_relu);

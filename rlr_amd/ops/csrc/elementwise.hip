@@ -6,6 +6,7 @@
 // (cdna_hip_programming.md Appendix B, Guideline 13).
 #include "common.h"
 #include "launchers.h"
+#include "tail_math.h"
 
 // ---------------------------------------------------------------- relu
 
@@ -203,10 +204,8 @@ __global__ void maxpool2x2_fwd_k(const T* __restrict__ x,
     const T* p = x + ((b * H + 2 * oh) * (long)W + 2 * ow) * C + c;
     float v00 = ldv(p), v01 = ldv(p + C), v10 = ldv(p + WC),
           v11 = ldv(p + WC + C);
-    float m = v00; uint8_t a = 0;
-    if (v01 > m) { m = v01; a = 1; }
-    if (v10 > m) { m = v10; a = 2; }
-    if (v11 > m) { m = v11; a = 3; }
+    float m; uint8_t a;
+    pool2x2_select(v00, v01, v10, v11, m, a);
     stv(&y[i], m);
     idx[i] = a;
   }
@@ -274,16 +273,16 @@ __global__ void maxpool2x2_bwd_gather4_k(const float* __restrict__ dy,
       const uint8_t* ap = idx + o;
       float4 d4 = *(const float4*)(dy + o);
       uint8_t a = ((ih & 1) << 1) | (iw & 1);
-      g.x = ap[0] == a ? d4.x : 0.f;
-      g.y = ap[1] == a ? d4.y : 0.f;
-      g.z = ap[2] == a ? d4.z : 0.f;
-      g.w = ap[3] == a ? d4.w : 0.f;
+      g.x = pool_bwd_pick(ap[0], a, d4.x);
+      g.y = pool_bwd_pick(ap[1], a, d4.y);
+      g.z = pool_bwd_pick(ap[2], a, d4.z);
+      g.w = pool_bwd_pick(ap[3], a, d4.w);
       if (relu_pooled) {
         float4 p4 = *(const float4*)(relu_pooled + o);
-        g.x = p4.x > 0.f ? g.x : 0.f;
-        g.y = p4.y > 0.f ? g.y : 0.f;
-        g.z = p4.z > 0.f ? g.z : 0.f;
-        g.w = p4.w > 0.f ? g.w : 0.f;
+        g.x = relu_gate(p4.x, g.x);
+        g.y = relu_gate(p4.y, g.y);
+        g.z = relu_gate(p4.z, g.z);
+        g.w = relu_gate(p4.w, g.w);
       }
     }
     *(float4*)(dx + i4 * 4) = g;
@@ -462,7 +461,7 @@ __global__ void dropout_fwd_k(const float* __restrict__ x,
                               float* __restrict__ y,
                               uint8_t* __restrict__ mask, long n, float p,
                               uint64_t seed, uint64_t offset) {
-  float scale = 1.0f / (1.0f - p);
+  float scale = dropout_scale(p);
   long stride = (long)gridDim.x * blockDim.x;
   long n4 = (n + 3) / 4;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
@@ -473,9 +472,9 @@ __global__ void dropout_fwd_k(const float* __restrict__ x,
     for (int j = 0; j < 4; ++j) {
       long k = i * 4 + j;
       if (k < n) {
-        bool keep = u32_to_uniform(rv[j]) >= p;
+        bool keep = dropout_keep(rv[j], p);
         mask[k] = keep;
-        y[k] = keep ? x[k] * scale : 0.f;
+        y[k] = dropout_apply(keep, x[k], scale);
       }
     }
   }
@@ -492,7 +491,7 @@ __global__ void dropout_fwd_dev_k(const float* __restrict__ x,
                                       state, int site) {
   uint64_t seed = state[0];
   uint64_t offset = state[1] + site;
-  float scale = 1.0f / (1.0f - p);
+  float scale = dropout_scale(p);
   long stride = (long)gridDim.x * blockDim.x;
   long n4 = (n + 3) / 4;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4;
@@ -503,9 +502,9 @@ __global__ void dropout_fwd_dev_k(const float* __restrict__ x,
     for (int j = 0; j < 4; ++j) {
       long k = i * 4 + j;
       if (k < n) {
-        bool keep = u32_to_uniform(rv[j]) >= p;
+        bool keep = dropout_keep(rv[j], p);
         mask[k] = keep;
-        y[k] = keep ? x[k] * scale : 0.f;
+        y[k] = dropout_apply(keep, x[k], scale);
       }
     }
   }
@@ -514,11 +513,11 @@ __global__ void dropout_fwd_dev_k(const float* __restrict__ x,
 __global__ void dropout_bwd_k(const float* __restrict__ dy,
                               const uint8_t* __restrict__ mask,
                               float* __restrict__ dx, long n, float p) {
-  float scale = 1.0f / (1.0f - p);
+  float scale = dropout_scale(p);
   long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride)
-    dx[i] = mask[i] ? dy[i] * scale : 0.f;
+    dx[i] = dropout_apply(mask[i], dy[i], scale);
 }
 
 // fused dropout+relu backward (manual tape): out = (y>0) * dropout_bwd —
@@ -527,11 +526,11 @@ __global__ void dropout_relu_bwd_k(const float* __restrict__ dy,
                                    const uint8_t* __restrict__ mask,
                                    const float* __restrict__ y,
                                    float* __restrict__ dx, long n, float p) {
-  float scale = 1.0f / (1.0f - p);
+  float scale = dropout_scale(p);
   long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride)
-    dx[i] = (y[i] > 0.f && mask[i]) ? dy[i] * scale : 0.f;
+    dx[i] = dropout_relu_gate(y[i], mask[i], dy[i], scale);
 }
 
 extern "C" {
@@ -571,21 +570,13 @@ __global__ void ce_fwd_k(const float* __restrict__ logits,
   int lane = threadIdx.x % kWave;
   if (row >= B) return;
   float v = (lane < C) ? logits[(long)row * C + lane] : -3.4e38f;
-  float m = v;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-    m = fmaxf(m, __shfl_xor(m, off, kWave));
-  float e = (lane < C) ? __expf(v - m) : 0.f;
-  float sum = e;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-    sum += __shfl_xor(sum, off, kWave);
-  float sm = e / sum;
+  float sm, m, sum;
+  ce_row_softmax(v, lane < C, sm, m, sum);
   if (lane < C) softmax[(long)row * C + lane] = sm;
   if (lane == 0) {
     long t = labels[row];
     float lt = logits[(long)row * C + t];
-    row_loss[row] = logf(sum) + m - lt;
+    row_loss[row] = ce_row_loss(sum, m, lt);
   }
 }
 
@@ -593,15 +584,8 @@ __global__ void ce_fwd_k(const float* __restrict__ logits,
 __global__ void ce_reduce_k(const float* __restrict__ row_loss,
                             float* __restrict__ out, int B) {
   __shared__ float sh[kBlock];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < B; i += blockDim.x) acc += row_loss[i];
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (int off = kBlock / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = sh[0] / B;
+  float mean = ce_mean_block(row_loss, B, sh);
+  if (threadIdx.x == 0) out[0] = mean;
 }
 
 // dlogits = dloss * (softmax - onehot) / B
@@ -616,8 +600,7 @@ __global__ void ce_bwd_k(const float* __restrict__ softmax,
        i += stride) {
     int c = i % C;
     long row = i / C;
-    float v = softmax[i] - (labels[row] == c ? 1.f : 0.f);
-    dlogits[i] = g * v / B;
+    dlogits[i] = ce_grad(g, softmax[i], labels[row] == c, B);
   }
 }
 

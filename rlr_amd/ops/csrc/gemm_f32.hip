@@ -18,6 +18,7 @@
 // combines them.  No atomics anywhere: bitwise run-to-run reproducible.
 #include "common.h"
 #include "launchers.h"
+#include "tail_math.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -314,16 +315,8 @@ __global__ void gemm_small_k(const float* __restrict__ A,
     const long astep = layout == 1 ? lda : 1;
     const float* b = layout == 2 ? B + (long)n * ldb : B + n;
     const long bstep = layout == 2 ? 1 : ldb;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int k = 0;
-    for (; k + 3 < K; k += 4) {
-      a0 = fmaf(a[(k + 0) * astep], b[(k + 0) * bstep], a0);
-      a1 = fmaf(a[(k + 1) * astep], b[(k + 1) * bstep], a1);
-      a2 = fmaf(a[(k + 2) * astep], b[(k + 2) * bstep], a2);
-      a3 = fmaf(a[(k + 3) * astep], b[(k + 3) * bstep], a3);
-    }
-    for (; k < K; ++k) a0 = fmaf(a[k * astep], b[k * bstep], a0);
-    float acc = (a0 + a1) + (a2 + a3);
+    float acc = dot_rot4(K, [&](int k) { return a[k * astep]; },
+                         [&](int k) { return b[k * bstep]; });
     if (bias) acc += bias[n];
     if (relu) acc = fmaxf(acc, 0.f);
     C[(long)m * ldc + n] = acc;
@@ -349,12 +342,9 @@ __global__ void gemm_small_wave_k(const float* __restrict__ A,
   const long astep = layout == 1 ? lda : 1;
   const float* b = layout == 2 ? B + (long)n * ldb : B + n;
   const long bstep = layout == 2 ? 1 : ldb;
-  float acc = 0.f;
-  for (int k = lane; k < K; k += kWave)
-    acc = fmaf(a[k * astep], b[k * bstep], acc);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-    acc += __shfl_down(acc, off, kWave);
+  float acc = dot_wave_partial(K, lane, [&](int k) { return a[k * astep]; },
+                               [&](int k) { return b[k * bstep]; });
+  acc = wave_tree_down(acc);
   if (lane == 0) {
     if (bias) acc += bias[n];
     if (relu) acc = fmaxf(acc, 0.f);
@@ -371,10 +361,7 @@ __global__ void colsum_k(const float* __restrict__ dY,
   int n = blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
   int lane = threadIdx.x % kWave;
   if (n >= N) return;
-  float acc = 0.f;
-  for (int m = lane; m < M; m += kWave) acc += dY[(long)m * N + n];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, kWave);
+  float acc = colsum_wave(dY, M, N, n, lane);
   if (lane == 0) db[n] = acc;
 }
 

@@ -91,6 +91,35 @@ void launch_nhwc_flatten_bf16(const unsigned short* in, unsigned short* out,
 void launch_nhwc_unflatten_bf16(const unsigned short* in,
                                 unsigned short* out, long B, int C, int H,
                                 int W, void* s);
+// fused_tail.hip (fp32).  The seam between the conv trunk and the first
+// fc layer: x (B,H,W,C) NHWC -> pooled / idx (B,H/2,W/2,C) NHWC and the
+// dropped flat-CHW rows d / mask (B, C*(H/2)*(W/2)), and its backward.
+// Both need pool_seam_fused_ok(C, H, W): C % 4 == 0 and the pooled image
+// fits the kernels' static LDS tile.
+int pool_seam_fused_ok(int C, int H, int W);
+void launch_pool_flatten_dropout_fwd(const float* x, float* pooled,
+                                     uint8_t* idx, float* d, uint8_t* mask,
+                                     long B, int H, int W, int C, float p,
+                                     const unsigned long long* state,
+                                     int site, void* s);
+void launch_dropout_unflatten_pool_bwd_relu(const float* g,
+                                            const uint8_t* mask,
+                                            const uint8_t* idx,
+                                            const float* pooled, float* dx,
+                                            long B, int H, int W, int C,
+                                            float p, void* s);
+// The classifier head on h1 (B,H), w (C,H), bias (C): dropout, fc, CE
+// forward and backward in two launches.  fc_head_fused_ok(B, H, C): C <= 64
+// and the three fc GEMMs all take launch_gemm_f32's tiny-problem branch.
+// ws: fc_head_ws_floats(B, H, C) floats.
+int fc_head_fused_ok(int B, int H, int C);
+long fc_head_ws_floats(int B, int H, int C);
+void launch_fc_head_step(const float* h1, const float* w, const float* bias,
+                         const long* labels, const float* dloss, float* ws,
+                         float* g_h1, float* dw, float* db, float* loss,
+                         int B, int H, int C, float p,
+                         const unsigned long long* state, int site,
+                         void* s);
 // flatopt.hip
 long flat_norm_scratch_floats();
 void launch_clipped_sgd(float* p, const float* g, float* v, float* scratch,
