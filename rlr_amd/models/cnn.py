@@ -25,6 +25,35 @@ class _OpsModel(nn.Module):
     def set_compute_dtype(self, dtype):
         self.compute_dtype = dtype
 
+    # True where manual_step takes bump_offset=True and then advances the
+    # device dropout offset itself, as the last thing of the step
+    # (engine.TrainEngine asks for it)
+    tape_bumps_offset = False
+
+    def _tape_begin(self, convs):
+        """Start of an fp32 manual tape: the queue its reductions wait on
+        and the step's conv weight permutes, ((weight, kind), ...) with
+        kind 0 = forward wt, 1 = bwd-data wp, in one launch.  Weights only
+        change in the optimizer kernels after the tape, so one permute per
+        step serves the forward and the backward.  (None, Nones) with
+        RLR_AMD_NO_STEP_BATCH=1: every kernel then runs stand-alone."""
+        from ..ops import ext, step_batching
+        if not step_batching():
+            return None, [None] * len(convs)
+        E = ext()
+        return E.StepQueue(), E.prep_conv_weights(list(convs))
+
+    def _tape_end(self, q, st, bump_offset):
+        """End of a manual tape: the queued folds in two launches; the
+        dropout-offset bump rides in the second one when asked for."""
+        if bump_offset:
+            if q is not None:
+                q.add_u64(st, 1, self.rng.SITE_STRIDE)
+            else:
+                st[1] += self.rng.SITE_STRIDE
+        if q is not None:
+            q.flush()
+
     def _cast_in(self, x):
         if self.compute_dtype is not None and x.dtype != self.compute_dtype:
             x = x.to(self.compute_dtype)
@@ -35,6 +64,8 @@ class CNN_MNIST(_OpsModel):
     """28x28x1: conv(1->32,3x3)+relu, conv(32->64,3x3)+relu, maxpool2,
     flatten 9216, dropout .5, fc 9216->128+relu, dropout, fc 128->10
     (reference models.py:11-31)."""
+
+    tape_bumps_offset = True
 
     def __init__(self):
         super().__init__()
@@ -56,17 +87,26 @@ class CNN_MNIST(_OpsModel):
         x = Fo.linear(x, self.fc2.weight, self.fc2.bias)
         return x
 
-    def manual_step(self, x, labels, dloss):
+    def manual_step(self, x, labels, dloss, bump_offset=False):
         """Hand-rolled fwd+bwd (fp32 GPU): identical kernel sequence to
         the autograd path, but weight/bias grads are written DIRECTLY into
         the preset p.grad flat-views (assignment == accumulate-into-zero,
-        bitwise) — no zero-grad fill, no autograd accumulate-adds."""
+        bitwise) — no zero-grad fill, no autograd accumulate-adds.
+
+        The folds of the backward (bias grads, split-K / chunk combines,
+        the head's stage B) wait on a StepQueue and run as two batched
+        launches at the end; every gradient is complete on return."""
         from ..ops import ext
         E = ext()
         p = self.p_drop
         st = self.rng.gpu_state(x.device)
-        a1 = E.conv2d_fwd(x, self.conv1.weight, self.conv1.bias, 1, 0, True)
-        a2 = E.conv2d_fwd(a1, self.conv2.weight, self.conv2.bias, 1, 0, True)
+        q, (wt1, wt2, wp2) = self._tape_begin((
+            (self.conv1.weight, 0), (self.conv2.weight, 0),
+            (self.conv2.weight, 1)))
+        a1 = E.conv2d_fwd(x, self.conv1.weight, self.conv1.bias, 1, 0, True,
+                          wt1)
+        a2 = E.conv2d_fwd(a1, self.conv2.weight, self.conv2.bias, 1, 0, True,
+                          wt2)
         # pool + flatten + dropout-1 in one kernel (ops/csrc/fused_tail.hip)
         pl, idx, d1, m1 = E.pool_flatten_dropout_fwd(a2, p, st, 0)
         h1 = E.linear_fwd(d1, self.fc1.weight, self.fc1.bias, True)
@@ -82,17 +122,19 @@ class CNN_MNIST(_OpsModel):
         # to fc1's relu mask) is two launches; the seam backward is one.
         loss, g = E.fc_head_step(h1, self.fc2.weight, self.fc2.bias, labels,
                                  dloss, p, st, 1, self.fc2.weight.grad,
-                                 self.fc2.bias.grad)
+                                 self.fc2.bias.grad, q)
         g = E.linear_bwd_into(d1, self.fc1.weight, g,
-                              self.fc1.weight.grad, self.fc1.bias.grad, True)
+                              self.fc1.weight.grad, self.fc1.bias.grad, True,
+                              q)
         g = E.dropout_unflatten_pool_bwd_relu(g, m1, idx, pl, p,
                                               list(a2.shape))
         g = E.conv2d_bwd_into(a1, self.conv2.weight, g, 1, 0, True,
                               self.conv2.weight.grad, self.conv2.bias.grad,
-                              a1)
+                              a1, wp2, q)
         E.conv2d_bwd_into(x, self.conv1.weight, g, 1, 0, False,
                           self.conv1.weight.grad, self.conv1.bias.grad,
-                          None)
+                          None, None, q)
+        self._tape_end(q, st, bump_offset)
         return loss
 
 
@@ -100,6 +142,8 @@ class CNN_CIFAR(_OpsModel):
     """32x32x3: 3 x [conv3x3 (3->64->128->256)+relu+maxpool2], flatten 1024,
     dropout-interleaved FCs 1024->128->256->10 (reference models.py:33-58;
     the reference's `64*4*4` flatten literal equals 256*2*2 = 1024)."""
+
+    tape_bumps_offset = True
 
     def __init__(self):
         super().__init__()
@@ -125,17 +169,24 @@ class CNN_CIFAR(_OpsModel):
         x = Fo.linear(x, self.fc3.weight, self.fc3.bias)
         return x
 
-    def manual_step(self, x, labels, dloss):
+    def manual_step(self, x, labels, dloss, bump_offset=False):
         """Hand-rolled fwd+bwd — see CNN_MNIST.manual_step."""
         from ..ops import ext
         E = ext()
         p = self.p_drop
         st = self.rng.gpu_state(x.device)
-        a1 = E.conv2d_fwd(x, self.conv1.weight, self.conv1.bias, 1, 0, True)
+        q, (wt1, wt2, wt3, wp2, wp3) = self._tape_begin((
+            (self.conv1.weight, 0), (self.conv2.weight, 0),
+            (self.conv3.weight, 0), (self.conv2.weight, 1),
+            (self.conv3.weight, 1)))
+        a1 = E.conv2d_fwd(x, self.conv1.weight, self.conv1.bias, 1, 0, True,
+                          wt1)
         p1, i1 = E.maxpool2x2_fwd(a1)
-        a2 = E.conv2d_fwd(p1, self.conv2.weight, self.conv2.bias, 1, 0, True)
+        a2 = E.conv2d_fwd(p1, self.conv2.weight, self.conv2.bias, 1, 0, True,
+                          wt2)
         p2, i2 = E.maxpool2x2_fwd(a2)
-        a3 = E.conv2d_fwd(p2, self.conv3.weight, self.conv3.bias, 1, 0, True)
+        a3 = E.conv2d_fwd(p2, self.conv3.weight, self.conv3.bias, 1, 0, True,
+                          wt3)
         p3, i3, d1, m1 = E.pool_flatten_dropout_fwd(a3, p, st, 0)
         h1 = E.linear_fwd(d1, self.fc1.weight, self.fc1.bias, True)
         d2, m2 = E.dropout_fwd_dev(h1, p, st, 1)
@@ -146,23 +197,26 @@ class CNN_CIFAR(_OpsModel):
         # following maxpool gather via the pooled values.
         loss, g = E.fc_head_step(h2, self.fc3.weight, self.fc3.bias, labels,
                                  dloss, p, st, 2, self.fc3.weight.grad,
-                                 self.fc3.bias.grad)
+                                 self.fc3.bias.grad, q)
         g = E.linear_bwd_into(d2, self.fc2.weight, g,
-                              self.fc2.weight.grad, self.fc2.bias.grad, True)
+                              self.fc2.weight.grad, self.fc2.bias.grad, True,
+                              q)
         g = E.dropout_relu_bwd(g, m2, h1, p)
         g = E.linear_bwd_into(d1, self.fc1.weight, g,
-                              self.fc1.weight.grad, self.fc1.bias.grad, True)
+                              self.fc1.weight.grad, self.fc1.bias.grad, True,
+                              q)
         g = E.dropout_unflatten_pool_bwd_relu(g, m1, i3, p3, p,
                                               list(a3.shape))
         g = E.conv2d_bwd_into(p2, self.conv3.weight, g, 1, 0, True,
                               self.conv3.weight.grad, self.conv3.bias.grad,
-                              None)
+                              None, wp3, q)
         g = E.maxpool2x2_bwd_relu(g, i2, p2, list(a2.shape))
         g = E.conv2d_bwd_into(p1, self.conv2.weight, g, 1, 0, True,
                               self.conv2.weight.grad, self.conv2.bias.grad,
-                              None)
+                              None, wp2, q)
         g = E.maxpool2x2_bwd_relu(g, i1, p1, list(a1.shape))
         E.conv2d_bwd_into(x, self.conv1.weight, g, 1, 0, False,
                           self.conv1.weight.grad, self.conv1.bias.grad,
-                          None)
+                          None, None, q)
+        self._tape_end(q, st, bump_offset)
         return loss

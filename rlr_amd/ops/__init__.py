@@ -38,6 +38,15 @@ def have_ext() -> bool:
         return False
 
 
+def step_batching() -> bool:
+    """Whether the fp32 manual tapes and the engine batch their small
+    kernels (ops/csrc/step_batch.hip): deferred reductions, one weight-prep
+    launch, one feed launch, the dropout-offset bump inside the step.
+    RLR_AMD_NO_STEP_BATCH=1 runs every kernel stand-alone instead; the
+    results are bitwise the same (tests/test_step_batch_gpu.py)."""
+    return os.environ.get('RLR_AMD_NO_STEP_BATCH', '0') != '1'
+
+
 def force_eager() -> bool:
     """Debug-only escape hatch; never set in production or benches."""
     return os.environ.get('RLR_AMD_FORCE_EAGER', '0') == '1'

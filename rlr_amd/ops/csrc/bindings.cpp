@@ -5,7 +5,9 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
+#include <algorithm>
 #include <cstdint>
+#include <vector>
 
 #include "launchers.h"
 
@@ -66,6 +68,175 @@ static const unsigned short* bfc(const torch::Tensor& t) {
 static unsigned short* bfp(const torch::Tensor& t) {
   return (unsigned short*)t.data_ptr();
 }
+
+// ------------------------------------------------------------- step queue
+// The fp32 manual tape's deferred small kernels (step_batch.hip).  An entry
+// point that is handed a queue launches only its main kernels and pushes
+// its folds here as roles; flush() issues level 1 (every first stage and
+// every single-stage final) and then level 2 (the second stages) as
+// role-batched launches.  Roles of one level never depend on each other.
+// The queue keeps every tensor a pending role touches alive until flush.
+struct StepQueue {
+  std::vector<StepRole> lv[2];
+  std::vector<torch::Tensor> held;
+  void* stream = nullptr;
+
+  void hold(const torch::Tensor& t) {
+    if (!t.defined()) return;
+    void* st = stream_of(t);
+    TORCH_CHECK(stream == nullptr || stream == st,
+                "StepQueue: roles of one flush must share a stream");
+    stream = st;
+    held.push_back(t);
+  }
+  void push(int level, const StepRole& r) { lv[level].push_back(r); }
+  std::tuple<int64_t, int64_t> pending() const {
+    return {(int64_t)lv[0].size(), (int64_t)lv[1].size()};
+  }
+  void flush() {
+    for (auto& level : lv) {
+      for (size_t i = 0; i < level.size(); i += kStepMaxRoles) {
+        size_t n = std::min(level.size() - i, (size_t)kStepMaxRoles);
+        TORCH_CHECK(launch_step_batch(level.data() + i, (int)n, stream) == 0,
+                    "StepQueue: more roles than one launch takes");
+      }
+      level.clear();
+    }
+    held.clear();
+    stream = nullptr;
+  }
+
+  static const float* f32c(const torch::Tensor& t) {
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat);
+    return t.data_ptr<float>();
+  }
+
+  // db_out (Kout) = column sums of dy, channels_last (Nb, Kout, OH, OW)
+  void conv_db(torch::Tensor dy, torch::Tensor db_out) {
+    TORCH_CHECK(dy.dim() == 4 &&
+                dy.is_contiguous(torch::MemoryFormat::ChannelsLast));
+    int Nb = dy.size(0), Kout = dy.size(1), OHW = dy.size(2) * dy.size(3);
+    TORCH_CHECK(db_out.is_contiguous() && db_out.numel() == Kout);
+    auto parts = torch::empty({conv_db_ws_floats(Kout)}, dy.options());
+    StepRole a, b;
+    conv_db_roles(f32c(dy), (float*)f32c(db_out), parts.data_ptr<float>(), Nb,
+                  Kout, OHW, &a, &b);
+    hold(dy); hold(db_out); hold(parts);
+    push(0, a);
+    push(1, b);
+  }
+  // launch_splitk_reduce_dwperm over ws (conv_dwperm_ws_floats layout)
+  void splitk_reduce_dwperm(torch::Tensor ws, torch::Tensor dw, int64_t Kout,
+                            int64_t C, int64_t RS, int64_t SK,
+                            int64_t ws_offset) {
+    TORCH_CHECK(dw.is_contiguous() && dw.numel() == Kout * C * RS);
+    StepRole a, b;
+    int levels = splitk_reduce_dwperm_roles(
+        f32c(ws) + ws_offset, (float*)f32c(dw), (int)Kout, (int)C, (int)RS,
+        (int)SK, &a, &b);
+    hold(ws); hold(dw);
+    push(0, a);
+    if (levels == 2) push(1, b);
+  }
+  // launch_splitk_reduce over ws; false (nothing queued) when the launcher
+  // would take its wave form, which has no role
+  bool splitk_reduce(torch::Tensor ws, torch::Tensor C,
+                     c10::optional<torch::Tensor> bias, int64_t M, int64_t N,
+                     int64_t ldc, int64_t SK, bool relu) {
+    StepRole a, b;
+    int levels = splitk_reduce_roles(
+        f32c(ws), (float*)f32c(C), bias ? f32c(*bias) : nullptr, (int)M,
+        (int)N, (int)ldc, (int)SK, relu ? 1 : 0, &a, &b);
+    if (levels == 0) return false;
+    hold(ws); hold(C);
+    if (bias) hold(*bias);
+    push(0, a);
+    if (levels == 2) push(1, b);
+    return true;
+  }
+  void colsum(torch::Tensor dy, torch::Tensor db_out) {
+    TORCH_CHECK(dy.dim() == 2 && dy.is_contiguous() &&
+                db_out.is_contiguous() && db_out.numel() == dy.size(1));
+    hold(dy); hold(db_out);
+    push(0, colsum_role(f32c(dy), (float*)f32c(db_out), (int)dy.size(0),
+                        (int)dy.size(1)));
+  }
+  // the combine of launch_conv_bwd_weight over the ws its main kernels wrote
+  void conv_bwd_weight_combine(torch::Tensor ws, torch::Tensor dw, int SK,
+                               int Nb, int C, int Kout, int R, int S, int OH,
+                               int OW) {
+    StepRole a, b;
+    int levels = conv_bwd_weight_combine_roles(
+        (float*)f32c(ws), (float*)f32c(dw), SK, Nb, C, Kout, R, S, OH, OW,
+        &a, &b);
+    hold(ws); hold(dw);
+    push(0, a);
+    if (levels == 2) push(1, b);
+  }
+  // the small-conv chunk partials (chunks, KO*C*RS) -> dw, as
+  // conv_bwd_weight_combine queues it for a layer with C*R*S <= 32
+  void conv_small_bwdw_reduce(torch::Tensor partials, torch::Tensor dw,
+                              int64_t Nb, int64_t C, int64_t Kout, int64_t R,
+                              int64_t S, int64_t OH, int64_t OW) {
+    TORCH_CHECK(C * R * S <= 32 && Kout <= 64);
+    conv_bwd_weight_combine(partials, dw, 1, (int)Nb, (int)C, (int)Kout,
+                            (int)R, (int)S, (int)OH, (int)OW);
+  }
+  // kind 0: the forward's wt (C*R*S, Kout); kind 1: bwd-data's wp
+  // (Kout*R*S, C)
+  torch::Tensor wperm(torch::Tensor w, int64_t kind) {
+    TORCH_CHECK(w.dim() == 4 && (kind == 0 || kind == 1));
+    w = w.contiguous();
+    int Kout = w.size(0), C = w.size(1), RS = w.size(2) * w.size(3);
+    auto out = kind == 0 ? torch::empty({(long)C * RS, Kout}, w.options())
+                         : torch::empty({(long)Kout * RS, C}, w.options());
+    hold(w); hold(out);
+    push(0, wperm_role((int)kind, f32c(w), out.data_ptr<float>(), Kout, C,
+                       RS));
+    return out;
+  }
+  // dst[r] = src[sel[r]] over dim 0; float or int64, rows dense and laid
+  // out alike in src and dst.  sel must index [0, src.size(0)): unlike
+  // index_select nothing asserts on the device; an index outside the range
+  // is not read, its row comes out as all-one bits (NaN / -1).
+  void gather_rows(torch::Tensor src, torch::Tensor sel, torch::Tensor dst) {
+    TORCH_CHECK(src.is_cuda() && dst.is_cuda() && sel.is_cuda());
+    TORCH_CHECK(sel.scalar_type() == torch::kInt64 && sel.is_contiguous());
+    TORCH_CHECK(src.scalar_type() == dst.scalar_type() &&
+                (src.scalar_type() == torch::kFloat ||
+                 src.scalar_type() == torch::kInt64));
+    TORCH_CHECK(src.dim() == dst.dim() && src.dim() >= 1 &&
+                dst.size(0) == sel.numel());
+    long row = src.dim() > 1 ? src.numel() / std::max<long>(src.size(0), 1)
+                             : 1;
+    TORCH_CHECK(src.is_non_overlapping_and_dense() &&
+                dst.is_non_overlapping_and_dense());
+    TORCH_CHECK(src.size(0) <= 1 || src.stride(0) == row);
+    TORCH_CHECK(dst.size(0) <= 1 || dst.stride(0) == row);
+    for (int d = 1; d < src.dim(); ++d)
+      TORCH_CHECK(src.size(d) == dst.size(d) &&
+                      (src.size(d) == 1 || src.stride(d) == dst.stride(d)),
+                  "gather_rows: src and dst rows must be laid out alike");
+    int words = (int)(row * (src.scalar_type() == torch::kInt64 ? 2 : 1));
+    hold(src); hold(sel); hold(dst);
+    TORCH_CHECK(src.size(0) <= INT32_MAX);
+    push(0, step_role_gather_rows(src.data_ptr(), sel.data_ptr<int64_t>(),
+                                  dst.data_ptr(), sel.numel(), words,
+                                  (int)src.size(0)));
+  }
+  // level 2: state[index] += delta (the dropout base offset of the next
+  // step, after every draw of this one)
+  void add_u64(torch::Tensor state, int64_t index, int64_t delta) {
+    TORCH_CHECK(state.is_cuda() && state.is_contiguous() &&
+                (state.scalar_type() == torch::kInt64 ||
+                 state.scalar_type() == torch::kUInt64) &&
+                index >= 0 && index < state.numel());
+    hold(state);
+    push(1, step_role_add_u64((unsigned long long*)state.data_ptr() + index,
+                              (unsigned long long)delta));
+  }
+};
+
 
 
 // ------------------------------------------------------------ elementwise
@@ -567,17 +738,29 @@ static torch::Tensor gemm_f32(const torch::Tensor& A, const torch::Tensor& B,
                               c10::optional<torch::Tensor> bias, bool relu,
                               int M, int N, int K, int lda, int ldb,
                               int layout,
-                              torch::Tensor C = torch::Tensor()) {
+                              torch::Tensor C = torch::Tensor(),
+                              StepQueue* q = nullptr) {
   if (!C.defined()) C = torch::empty({M, N}, A.options());
   int SK = gemm_f32_splitk(M, N, K);
   torch::Tensor ws;  // split-K slabs; none for SK == 1
   if (SK > 1)
     ws = torch::empty({gemm_splitk_ws_floats(M, N, SK)}, A.options());
-  launch_gemm_f32(A.data_ptr<float>(), B.data_ptr<float>(),
-                  C.data_ptr<float>(),
-                  bias ? bias->data_ptr<float>() : nullptr,
-                  SK > 1 ? ws.data_ptr<float>() : nullptr, M, N, K, lda, ldb,
-                  N, SK, relu ? 1 : 0, layout, stream_of(A));
+  const float* bp = bias ? bias->data_ptr<float>() : nullptr;
+  float* wsp = SK > 1 ? ws.data_ptr<float>() : nullptr;
+  if (!q) {
+    launch_gemm_f32(A.data_ptr<float>(), B.data_ptr<float>(),
+                    C.data_ptr<float>(), bp, wsp, M, N, K, lda, ldb, N, SK,
+                    relu ? 1 : 0, layout, stream_of(A));
+    return C;
+  }
+  // main kernel now; the split-K combine waits on the queue when the
+  // launcher's own predicates pick a form that has a role
+  if (launch_gemm_f32_main(A.data_ptr<float>(), B.data_ptr<float>(),
+                           C.data_ptr<float>(), bp, wsp, M, N, K, lda, ldb,
+                           N, SK, relu ? 1 : 0, layout, stream_of(A)) &&
+      !q->splitk_reduce(ws, C, bias, M, N, N, SK, relu))
+    launch_splitk_reduce(wsp, C.data_ptr<float>(), bp, M, N, N, SK,
+                         relu ? 1 : 0, stream_of(A));
   return C;
 }
 
@@ -644,7 +827,7 @@ torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w,
 torch::Tensor linear_bwd_into(torch::Tensor x, torch::Tensor w,
                               torch::Tensor dy, torch::Tensor dw_out,
                               c10::optional<torch::Tensor> db_out,
-                              bool need_dx) {
+                              bool need_dx, StepQueue* q = nullptr) {
   TORCH_CHECK(x.is_cuda() && !is_bf16(x));
   dy = dy.contiguous();
   x = x.contiguous();
@@ -654,10 +837,13 @@ torch::Tensor linear_bwd_into(torch::Tensor x, torch::Tensor w,
   torch::Tensor dx;
   if (need_dx)
     dx = gemm_f32(dy, w, c10::nullopt, false, bM, in, out, out, in, 0);
-  gemm_f32(dy, x, c10::nullopt, false, out, in, bM, out, in, 1, dw_out);
+  gemm_f32(dy, x, c10::nullopt, false, out, in, bM, out, in, 1, dw_out, q);
   if (db_out) {
     TORCH_CHECK(db_out->is_contiguous() && db_out->numel() == out);
-    launch_colsum(dy.data_ptr<float>(), db_out->data_ptr<float>(), bM, out,
+    if (q)
+      q->colsum(dy, *db_out);
+    else
+      launch_colsum(dy.data_ptr<float>(), db_out->data_ptr<float>(), bM, out,
                   stream_of(dy));
   }
   return dx;
@@ -676,7 +862,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> linear_bwd(
   }
   auto dw = torch::empty({w.size(0), w.size(1)}, dy.options());
   auto db = torch::empty({w.size(0)}, dy.options());
-  auto dx = linear_bwd_into(x, w, dy, dw, db, true);
+  auto dx = linear_bwd_into(x, w, dy, dw, db, true, nullptr);
   return {dx, dw, db};
 }
 
@@ -755,7 +941,7 @@ torch::Tensor dropout_unflatten_pool_bwd_relu(torch::Tensor g,
 std::tuple<torch::Tensor, torch::Tensor> fc_head_step(
     torch::Tensor h1, torch::Tensor w, torch::Tensor b, torch::Tensor labels,
     torch::Tensor dloss, double p, torch::Tensor state, int64_t site,
-    torch::Tensor dw_out, torch::Tensor db_out) {
+    torch::Tensor dw_out, torch::Tensor db_out, StepQueue* q = nullptr) {
   TORCH_CHECK(h1.is_cuda() && h1.dim() == 2 && !is_bf16(h1));
   int B = h1.size(0), H = h1.size(1), C = w.size(0);
   TORCH_CHECK(w.size(1) == H && b.numel() == C && labels.numel() == B);
@@ -766,7 +952,7 @@ std::tuple<torch::Tensor, torch::Tensor> fc_head_step(
     auto out = linear_fwd(d2, w, b, false);
     auto [loss, softmax] = cross_entropy_fwd(out, labels);
     auto g = cross_entropy_bwd(softmax, labels, dloss);
-    g = linear_bwd_into(d2, w, g, dw_out, db_out, true);
+    g = linear_bwd_into(d2, w, g, dw_out, db_out, true, q);
     return {loss, dropout_relu_bwd(g, m2, h1, p)};
   }
   h1 = h1.contiguous();
@@ -777,6 +963,19 @@ std::tuple<torch::Tensor, torch::Tensor> fc_head_step(
   auto ws = torch::empty({fc_head_ws_floats(B, H, C)}, h1.options());
   auto g_h1 = torch::empty_like(h1);
   auto loss = torch::empty({}, h1.options());
+  if (q) {  // stage A now, stage B as a level-1 role
+    launch_fc_head_rows(h1.data_ptr<float>(), w.data_ptr<float>(),
+                        b.data_ptr<float>(), labels.data_ptr<int64_t>(),
+                        dl.data_ptr<float>(), ws.data_ptr<float>(),
+                        g_h1.data_ptr<float>(), B, H, C, (float)p,
+                        dropout_state(state), (int)site, stream_of(h1));
+    q->hold(ws); q->hold(dw_out); q->hold(db_out); q->hold(loss);
+    q->push(0, fc_head_reduce_role(ws.data_ptr<float>(),
+                                   dw_out.data_ptr<float>(),
+                                   db_out.data_ptr<float>(),
+                                   loss.data_ptr<float>(), B, H, C));
+    return {loss, g_h1};
+  }
   launch_fc_head_step(h1.data_ptr<float>(), w.data_ptr<float>(),
                       b.data_ptr<float>(), labels.data_ptr<int64_t>(),
                       dl.data_ptr<float>(), ws.data_ptr<float>(),
@@ -791,8 +990,12 @@ std::tuple<torch::Tensor, torch::Tensor> fc_head_step(
 
 torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w,
                          c10::optional<torch::Tensor> b, int64_t stride,
-                         int64_t pad, bool relu) {
+                         int64_t pad, bool relu,
+                         c10::optional<torch::Tensor> wt_in = c10::nullopt) {
   TORCH_CHECK(x.is_cuda() && w.is_cuda());
+  // wt_in: the fp32 forward's permuted weights (StepQueue::wperm kind 0),
+  // made once per step by the caller instead of per call here
+  TORCH_CHECK(!wt_in || !is_bf16(x), "pre-permuted weights are fp32-only");
   x = cl(x, "conv_fwd.x");
   w = w.contiguous();
   int Nb = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
@@ -822,12 +1025,21 @@ torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w,
       return y;
     }
     // first-layer fallback (C=1,3): fp32 kernels, bf16 in/out casts
-    auto y32 = conv2d_fwd(x.to(torch::kFloat), w, b, stride, pad, relu);
+    auto y32 = conv2d_fwd(x.to(torch::kFloat), w, b, stride, pad, relu,
+                          c10::nullopt);
     return y32.to(torch::kBFloat16);
   }
-  auto wt = torch::empty({(long)C * R * S, Kout}, w.options());
-  launch_wperm_crs_ko(w.data_ptr<float>(), wt.data_ptr<float>(), Kout, C,
-                      R * S, stream_of(x));
+  torch::Tensor wt;
+  if (wt_in) {
+    wt = *wt_in;
+    TORCH_CHECK(wt.is_cuda() && wt.is_contiguous() &&
+                wt.scalar_type() == torch::kFloat &&
+                wt.numel() == w.numel());
+  } else {
+    wt = torch::empty({(long)C * R * S, Kout}, w.options());
+    launch_wperm_crs_ko(w.data_ptr<float>(), wt.data_ptr<float>(), Kout, C,
+                        R * S, stream_of(x));
+  }
   auto y = empty_cl({Nb, Kout, OH, OW}, x.options());
   launch_conv_fwd(x.data_ptr<float>(), wt.data_ptr<float>(), bp,
                   y.data_ptr<float>(), Nb, C, H, W, Kout, R, S, OH, OW,
@@ -873,7 +1085,15 @@ static torch::Tensor conv_bwd_core(torch::Tensor x, torch::Tensor w,
                                    int64_t pad, bool need_dx,
                                    torch::Tensor dw_out,
                                    c10::optional<torch::Tensor> db_out,
-                                   c10::optional<torch::Tensor> relu_y) {
+                                   c10::optional<torch::Tensor> relu_y,
+                                   c10::optional<torch::Tensor> wp_in =
+                                       c10::nullopt,
+                                   StepQueue* q = nullptr) {
+  // wp_in (fp32): bwd-data's permuted weights, made once per step by the
+  // caller (StepQueue::wperm kind 1).  q (fp32): the dw combine and the
+  // bias-gradient fold wait on the queue instead of launching here.
+  TORCH_CHECK((!wp_in && !q) || !is_bf16(x),
+              "pre-permuted weights and the step queue are fp32-only");
   x = cl(x, "conv_bwd.x");
   w = w.contiguous();
   dy = cl(dy, "conv_bwd.dy");
@@ -894,15 +1114,23 @@ static torch::Tensor conv_bwd_core(torch::Tensor x, torch::Tensor w,
 
   torch::Tensor dx;
   if (need_dx) {
-    auto wp = torch::empty(
-        {(long)Kout * R * S, C},
-        bf ? w.options().dtype(torch::kBFloat16) : w.options());
-    if (bf)
-      launch_wperm_rsko_c_bf16(w.data_ptr<float>(), bfp(wp), Kout, C, R * S,
-                               st);
-    else
-      launch_wperm_kors_c(w.data_ptr<float>(), wp.data_ptr<float>(), Kout,
-                          C, R * S, st);
+    torch::Tensor wp;
+    if (wp_in) {
+      wp = *wp_in;
+      TORCH_CHECK(wp.is_cuda() && wp.is_contiguous() &&
+                  wp.scalar_type() == torch::kFloat &&
+                  wp.numel() == w.numel());
+    } else {
+      wp = torch::empty(
+          {(long)Kout * R * S, C},
+          bf ? w.options().dtype(torch::kBFloat16) : w.options());
+      if (bf)
+        launch_wperm_rsko_c_bf16(w.data_ptr<float>(), bfp(wp), Kout, C,
+                                 R * S, st);
+      else
+        launch_wperm_kors_c(w.data_ptr<float>(), wp.data_ptr<float>(), Kout,
+                            C, R * S, st);
+    }
     dx = empty_cl({Nb, C, H, W}, x.options());
     torch::Tensor ryt;
     if (relu_y) ryt = cl(*relu_y, "conv_bwd.relu_y");
@@ -938,13 +1166,25 @@ static torch::Tensor conv_bwd_core(torch::Tensor x, torch::Tensor w,
     int SK = conv_bwd_weight_splitk(Kout, Ncrs, Kdim);
     auto ws = torch::empty({conv_bwd_weight_ws_floats(Kout, Ncrs, SK)},
                            w.options());
-    launch_conv_bwd_weight(dy.data_ptr<float>(), x.data_ptr<float>(),
-                           dw_out.data_ptr<float>(), ws.data_ptr<float>(),
-                           SK, Nb, C, H, W, Kout, R, S, OH, OW, st_, pd, st);
+    if (q) {
+      launch_conv_bwd_weight_main(dy.data_ptr<float>(), x.data_ptr<float>(),
+                                  ws.data_ptr<float>(), SK, Nb, C, H, W,
+                                  Kout, R, S, OH, OW, st_, pd, st);
+      q->conv_bwd_weight_combine(ws, dw_out, SK, Nb, C, Kout, R, S, OH, OW);
+    } else {
+      launch_conv_bwd_weight(dy.data_ptr<float>(), x.data_ptr<float>(),
+                             dw_out.data_ptr<float>(), ws.data_ptr<float>(),
+                             SK, Nb, C, H, W, Kout, R, S, OH, OW, st_, pd,
+                             st);
+    }
   }
 
   if (db_out) {
     TORCH_CHECK(db_out->is_contiguous() && db_out->numel() == Kout);
+    if (q) {
+      q->conv_db(dy, *db_out);
+      return dx;
+    }
     auto parts = torch::empty({conv_db_ws_floats(Kout)}, w.options());
     if (bf)
       launch_conv_db_bf16(bfc(dy), db_out->data_ptr<float>(),
@@ -981,11 +1221,13 @@ torch::Tensor conv2d_bwd_into(torch::Tensor x, torch::Tensor w,
                               torch::Tensor dy, int64_t stride, int64_t pad,
                               bool need_dx, torch::Tensor dw_out,
                               c10::optional<torch::Tensor> db_out,
-                              c10::optional<torch::Tensor> relu_y) {
+                              c10::optional<torch::Tensor> relu_y,
+                              c10::optional<torch::Tensor> wp = c10::nullopt,
+                              StepQueue* q = nullptr) {
   TORCH_CHECK(x.is_cuda() && !is_bf16(x));
   TORCH_CHECK(dw_out.is_contiguous() && dw_out.numel() == w.numel());
   return conv_bwd_core(x, w, dy, stride, pad, need_dx, dw_out, db_out,
-                       relu_y);
+                       relu_y, wp, q);
 }
 
 // bf16/fp32 conv backward with dw written into a caller-owned view and
@@ -1131,6 +1373,122 @@ torch::Tensor normalize_u8(torch::Tensor raw, torch::Tensor mean,
   return out;
 }
 
+// ------------------------------------------------------------ step batch
+
+// One launch for every conv weight permute of a step: (weight, kind) pairs,
+// kind 0 = the forward's wt, 1 = bwd-data's wp (StepQueue::wperm).  Valid
+// until the weights next change (the optimizer kernels at the step's end).
+std::vector<torch::Tensor> prep_conv_weights(
+    std::vector<std::pair<torch::Tensor, int64_t>> items) {
+  StepQueue q;
+  std::vector<torch::Tensor> out;
+  out.reserve(items.size());
+  for (auto& it : items) out.push_back(q.wperm(it.first, it.second));
+  q.flush();
+  return out;
+}
+
+// The step's feed in one launch: out_x = X[sel], out_y = Y[sel] (dim 0);
+// sel must index the rows of X and Y (StepQueue::gather_rows).
+void feed_gather(torch::Tensor X, torch::Tensor Y, torch::Tensor sel,
+                 torch::Tensor out_x, torch::Tensor out_y) {
+  StepQueue q;
+  q.gather_rows(X, sel, out_x);
+  q.gather_rows(Y, sel, out_y);
+  q.flush();
+}
+
+// The stand-alone launchers of the batched roles, one binding each, so a
+// test can hold a role against the kernel it shares its body with.
+torch::Tensor conv_db(torch::Tensor dy) {
+  TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 && !is_bf16(dy));
+  dy = cl(dy, "conv_db.dy");
+  int Nb = dy.size(0), Kout = dy.size(1), OHW = dy.size(2) * dy.size(3);
+  auto db = torch::empty({Kout}, dy.options());
+  auto parts = torch::empty({conv_db_ws_floats(Kout)}, dy.options());
+  launch_conv_db(dy.data_ptr<float>(), db.data_ptr<float>(),
+                 parts.data_ptr<float>(), Nb, Kout, OHW, stream_of(dy));
+  return db;
+}
+
+torch::Tensor splitk_reduce_dwperm(torch::Tensor ws, int64_t Kout, int64_t C,
+                                   int64_t RS, int64_t SK) {
+  CHK_CUDA(ws);
+  TORCH_CHECK(ws.numel() >= conv_dwperm_ws_floats(Kout, C * RS, SK));
+  auto dw = torch::empty({Kout * C * RS}, ws.options());
+  launch_splitk_reduce_dwperm(ws.data_ptr<float>(), dw.data_ptr<float>(),
+                              (int)Kout, (int)C, (int)RS, (int)SK,
+                              stream_of(ws));
+  return dw;
+}
+
+torch::Tensor splitk_reduce(torch::Tensor ws, int64_t M, int64_t N,
+                            int64_t SK) {
+  CHK_CUDA(ws);
+  TORCH_CHECK(ws.numel() >= gemm_splitk_ws_floats(M, N, SK));
+  auto C = torch::empty({M, N}, ws.options());
+  launch_splitk_reduce(ws.data_ptr<float>(), C.data_ptr<float>(), nullptr,
+                       (int)M, (int)N, (int)N, (int)SK, 0, stream_of(ws));
+  return C;
+}
+
+// chunk partials of a (C*R*S <= 32) layer's backward-weight -> dw, through
+// launch_conv_bwd_weight's own combine
+torch::Tensor conv_small_bwdw_reduce(torch::Tensor partials, int64_t Nb,
+                                     int64_t C, int64_t Kout, int64_t R,
+                                     int64_t S, int64_t OH, int64_t OW) {
+  CHK_CUDA(partials);
+  TORCH_CHECK(C * R * S <= 32 && Kout <= 64);
+  StepRole a, b;
+  auto dw = torch::empty({Kout * C * R * S}, partials.options());
+  conv_bwd_weight_combine_roles(partials.data_ptr<float>(),
+                                dw.data_ptr<float>(), 1, (int)Nb, (int)C,
+                                (int)Kout, (int)R, (int)S, (int)OH, (int)OW,
+                                &a, &b);
+  TORCH_CHECK(partials.numel() >= (int64_t)a.i[3] * Kout * C * R * S);
+  launch_conv_small_bwdw_reduce(partials.data_ptr<float>(),
+                                dw.data_ptr<float>(), (int)Kout, (int)C,
+                                (int)(R * S), a.i[3], stream_of(partials));
+  return dw;
+}
+
+torch::Tensor colsum(torch::Tensor dy) {
+  CHK_CUDA(dy);
+  TORCH_CHECK(dy.dim() == 2 && dy.is_contiguous());
+  auto db = torch::empty({dy.size(1)}, dy.options());
+  launch_colsum(dy.data_ptr<float>(), db.data_ptr<float>(), (int)dy.size(0),
+                (int)dy.size(1), stream_of(dy));
+  return db;
+}
+
+torch::Tensor wperm(torch::Tensor w, int64_t kind) {
+  TORCH_CHECK(w.is_cuda() && w.dim() == 4 && (kind == 0 || kind == 1));
+  w = w.contiguous();
+  int Kout = w.size(0), C = w.size(1), RS = w.size(2) * w.size(3);
+  auto out = kind == 0 ? torch::empty({(long)C * RS, Kout}, w.options())
+                       : torch::empty({(long)Kout * RS, C}, w.options());
+  (kind == 0 ? launch_wperm_crs_ko : launch_wperm_kors_c)(
+      w.data_ptr<float>(), out.data_ptr<float>(), Kout, C, RS, stream_of(w));
+  return out;
+}
+
+// (first block of each role, total blocks) of a batched launch
+std::tuple<std::vector<int64_t>, int64_t> step_batch_plan_py(
+    std::vector<int64_t> counts) {
+  std::vector<int> c(counts.begin(), counts.end()), f(counts.size());
+  int total = step_batch_plan(c.data(), (int)c.size(), f.data());
+  return {std::vector<int64_t>(f.begin(), f.end()), (int64_t)total};
+}
+
+// (role, block inside the role) that flat block `block` runs; role -1: none
+std::tuple<int64_t, int64_t> step_batch_lookup_py(std::vector<int64_t> counts,
+                                                  int64_t block) {
+  std::vector<int> c(counts.begin(), counts.end());
+  int v = -1;
+  int r = step_batch_lookup(c.data(), (int)c.size(), (int)block, &v);
+  return {(int64_t)r, (int64_t)(r < 0 ? -1 : v)};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1171,10 +1529,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("nhwc_unflatten", &nhwc_unflatten);
   m.def("linear_fwd", &linear_fwd);
   m.def("linear_bwd", &linear_bwd);
-  m.def("conv2d_fwd", &conv2d_fwd);
+  m.def("conv2d_fwd", &conv2d_fwd, py::arg("x"), py::arg("w"), py::arg("b"),
+        py::arg("stride"), py::arg("pad"), py::arg("relu"),
+        py::arg("wt") = py::none());
   m.def("conv2d_bwd", &conv2d_bwd);
-  m.def("conv2d_bwd_into", &conv2d_bwd_into);
-  m.def("linear_bwd_into", &linear_bwd_into);
+  m.def("conv2d_bwd_into", &conv2d_bwd_into, py::arg("x"), py::arg("w"),
+        py::arg("dy"), py::arg("stride"), py::arg("pad"), py::arg("need_dx"),
+        py::arg("dw_out"), py::arg("db_out"), py::arg("relu_y"),
+        py::arg("wp") = py::none(), py::arg("queue") = py::none());
+  m.def("linear_bwd_into", &linear_bwd_into, py::arg("x"), py::arg("w"),
+        py::arg("dy"), py::arg("dw_out"), py::arg("db_out"),
+        py::arg("need_dx"), py::arg("queue") = py::none());
   m.def("dropout_relu_bwd", &dropout_relu_bwd);
   m.def("batchnorm_bwd_into", &batchnorm_bwd_into);
   m.def("conv2d_bwd_wdx_into", &conv2d_bwd_wdx_into);
@@ -1223,7 +1588,38 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("pool_flatten_dropout_fwd", &pool_flatten_dropout_fwd);
   m.def("dropout_unflatten_pool_bwd_relu", &dropout_unflatten_pool_bwd_relu);
-  m.def("fc_head_step", &fc_head_step);
+  m.def("fc_head_step", &fc_head_step, py::arg("h1"), py::arg("w"),
+        py::arg("b"), py::arg("labels"), py::arg("dloss"), py::arg("p"),
+        py::arg("state"), py::arg("site"), py::arg("dw_out"),
+        py::arg("db_out"), py::arg("queue") = py::none());
+  // step batching (step_batch.hip): the queue of deferred roles, the two
+  // one-launch helpers built on it, the stand-alone launcher of each role
+  // and the launch plan (host arithmetic only)
+  py::class_<StepQueue>(m, "StepQueue")
+      .def(py::init<>())
+      .def("flush", &StepQueue::flush)
+      .def("pending", &StepQueue::pending)
+      .def("conv_db", &StepQueue::conv_db)
+      .def("splitk_reduce_dwperm", &StepQueue::splitk_reduce_dwperm,
+           py::arg("ws"), py::arg("dw"), py::arg("Kout"), py::arg("C"),
+           py::arg("RS"), py::arg("SK"), py::arg("ws_offset") = 0)
+      .def("splitk_reduce", &StepQueue::splitk_reduce)
+      .def("colsum", &StepQueue::colsum)
+      .def("conv_small_bwdw_reduce", &StepQueue::conv_small_bwdw_reduce)
+      .def("wperm", &StepQueue::wperm)
+      .def("gather_rows", &StepQueue::gather_rows)
+      .def("add_u64", &StepQueue::add_u64);
+  m.def("prep_conv_weights", &prep_conv_weights);
+  m.def("feed_gather", &feed_gather);
+  m.def("conv_db", &conv_db);
+  m.def("splitk_reduce_dwperm", &splitk_reduce_dwperm);
+  m.def("splitk_reduce", &splitk_reduce);
+  m.def("conv_small_bwdw_reduce", &conv_small_bwdw_reduce);
+  m.def("colsum", &colsum);
+  m.def("wperm", &wperm);
+  m.def("step_batch_max_roles", &step_batch_max_roles);
+  m.def("step_batch_plan", &step_batch_plan_py);
+  m.def("step_batch_lookup", &step_batch_lookup_py);
   m.def("pool_seam_fused_ok", &pool_seam_fused_ok);
   m.def("fc_head_fused_ok", &fc_head_fused_ok);
   m.def("fc_head_ws_floats", &fc_head_ws_floats);

@@ -20,6 +20,7 @@
 // wp[(r,s,ko)][c].  All reductions fixed-order; no atomics.
 #include "common.h"
 #include "launchers.h"
+#include "step_roles.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -1115,25 +1116,11 @@ void conv_small_bwdw_k(const float* __restrict__ dy,
 }
 
 // combine partials (fixed order, wave per pair) + permute (r,s,c)->(c,r,s)
+// (body: step_roles.h, shared with the role-batched launch)
 __global__ void conv_small_bwdw_reduce_k(const float* __restrict__ partials,
                                          float* __restrict__ dw, int KO,
                                          int C, int RS, int chunks) {
-  int pairs = KO * C * RS;
-  int p = blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
-  int lane = threadIdx.x % kWave;
-  if (p >= pairs) return;
-  float acc = 0.f;
-  for (int ch = lane; ch < chunks; ch += kWave)
-    acc += partials[(long)ch * pairs + p];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, kWave);
-  if (lane == 0) {
-    int crs = p % (C * RS);   // (r,s,c)
-    int ko = p / (C * RS);
-    int c = crs % C;
-    int rs = crs / C;
-    dw[(ko * C + c) * RS + rs] = acc;
-  }
+  conv_small_bwdw_reduce_body(blockIdx.x, partials, dw, KO, C, RS, chunks);
 }
 
 // fused split-K combine + dw permute: sums the SK rsc-ordered slabs and
@@ -1142,27 +1129,7 @@ __global__ void conv_small_bwdw_reduce_k(const float* __restrict__ partials,
 __global__ void splitk_reduce_dwperm_k(const float* __restrict__ ws,
                                        float* __restrict__ dw, int Kout,
                                        int C, int RS, int SK) {
-  long n_out = (long)Kout * C * RS;
-  long stride = (long)gridDim.x * blockDim.x;
-  int CRS = C * RS;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_out;
-       i += stride) {
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int z = 0;
-    for (; z + 3 < SK; z += 4) {
-      a0 += ws[(long)z * n_out + i];
-      a1 += ws[(long)(z + 1) * n_out + i];
-      a2 += ws[(long)(z + 2) * n_out + i];
-      a3 += ws[(long)(z + 3) * n_out + i];
-    }
-    for (; z < SK; ++z) a0 += ws[(long)z * n_out + i];
-    float acc = (a0 + a1) + (a2 + a3);
-    int col = i % CRS;  // (r,s,c) flat: rs*C + c
-    long ko = i / CRS;
-    int c = col % C;
-    int rs = col / C;
-    dw[(ko * C + c) * RS + rs] = acc;
-  }
+  splitk_reduce_dwperm_body(blockIdx.x, gridDim.x, ws, dw, Kout, C, RS, SK);
 }
 
 // dw column permute: [(ko)][(r,s,c)] -> torch layout [(ko)][(c,r,s)]
@@ -1190,65 +1157,28 @@ __global__ void dwperm_rsc_crs_k(const float* __restrict__ in,
 __global__ void conv_db_stage1_k(const float* __restrict__ dy,
                                  float* __restrict__ partials, long M,
                                  int Kout, int chunks, int K_blk) {
-  int sub_per = blockDim.x / K_blk;
-  int ko = blockIdx.y * K_blk + threadIdx.x % K_blk;
-  int chunk = blockIdx.x * sub_per + threadIdx.x / K_blk;
-  if (ko >= Kout || chunk >= chunks) return;
-  long per = (M + chunks - 1) / chunks;
-  long lo = (long)chunk * per, hi = min(M, lo + per);
-  float acc = 0.f;
-#pragma unroll 4
-  for (long m = lo; m < hi; ++m) acc += dy[m * Kout + ko];
-  partials[(long)chunk * Kout + ko] = acc;
+  conv_db_stage1_body(blockIdx.x, blockIdx.y, dy, partials, M, Kout, chunks,
+                      K_blk);
 }
 
 __global__ void conv_db_stage2_k(const float* __restrict__ partials,
                                  float* __restrict__ db, int Kout,
                                  int chunks) {
-  // one BLOCK per ko: 256 threads stride the chunks, LDS tree combine
-  int ko = blockIdx.x;
   __shared__ float sh[kBlock];
-  float acc = 0.f;
-  for (int c = threadIdx.x; c < chunks; c += blockDim.x)
-    acc += partials[(long)c * Kout + ko];
-  sh[threadIdx.x] = acc;
-  __syncthreads();
-  for (int off = kBlock / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) db[ko] = sh[0];
+  conv_db_stage2_body(blockIdx.x, partials, db, Kout, chunks, sh);
 }
 
 // permute w (Kout,C,R,S) -> staged layouts
 __global__ void wperm_rsc_ko_k(const float* __restrict__ w,
                                float* __restrict__ out, int Kout, int C,
                                int RS) {
-  // out[((rs)*C + c)*Kout + ko] = w[(ko*C + c)*RS + rs]
-  long n = (long)Kout * C * RS;
-  long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride) {
-    int rs = i % RS;
-    int c = (i / RS) % C;
-    long ko = i / ((long)RS * C);
-    out[((long)rs * C + c) * Kout + ko] = w[i];
-  }
+  wperm_rsc_ko_body(blockIdx.x, gridDim.x, w, out, Kout, C, RS);
 }
 
 __global__ void wperm_rsko_c_k(const float* __restrict__ w,
                                float* __restrict__ out, int Kout, int C,
                                int RS) {
-  // out[((rs)*Kout + ko)*C + c] = w[(ko*C + c)*RS + rs]
-  long n = (long)Kout * C * RS;
-  long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride) {
-    int rs = i % RS;
-    int c = (i / RS) % C;
-    long ko = i / ((long)RS * C);
-    out[((long)rs * Kout + ko) * C + c] = w[i];
-  }
+  wperm_rsko_c_body(blockIdx.x, gridDim.x, w, out, Kout, C, RS);
 }
 
 extern "C" {
@@ -1372,11 +1302,27 @@ long conv_bwd_weight_ws_floats(int Kout, int Ncrs, int SK) {
   return conv_dwperm_ws_floats(Kout, Ncrs, SK);
 }
 
-// ws: conv_bwd_weight_ws_floats(Kout, Ncrs, SK) floats
-void launch_conv_bwd_weight(const float* dy, const float* x, float* dw,
-                            float* ws, int SK, int Nb, int C, int H, int W,
-                            int Kout, int R, int S, int OH, int OW,
-                            int stride, int pad, void* s) {
+// one 128-row tile per block where possible: 512 fixed chunks left the
+// chip at 2 blocks/CU (48 KB LDS, 4 waves) — finer chunking trades a
+// longer fixed-order reduce for 3x the resident parallelism
+static int conv_small_bwdw_chunks(long Kdim) {
+  int chunks = (int)min((Kdim + 127) / 128, (long)kSmallBwdwMaxChunks);
+  return chunks < 64 ? 64 : chunks;
+}
+
+// what the main kernels of launch_conv_bwd_weight wrote, still to combine:
+// the slabs (or, for SK == 1, the rsc temp) of the split-K layout
+static float* conv_bwdw_target(float* ws, int SK, int Kout, int Ncrs) {
+  return SK == 1 ? ws + (long)SK * Kout * Ncrs : ws;
+}
+
+// The main kernels only: chunk partials (small path) or split-K slabs into
+// ws.  launch_conv_bwd_weight_combine, or the roles of
+// conv_bwd_weight_combine_roles, finish dw from them.
+void launch_conv_bwd_weight_main(const float* dy, const float* x, float* ws,
+                                 int SK, int Nb, int C, int H, int W,
+                                 int Kout, int R, int S, int OH, int OW,
+                                 int stride, int pad, void* s) {
   ConvShape sh{Nb, C, H, W, Kout, R, S, OH, OW, stride, pad};
   int Ncrs = C * R * S;
   long Kdim = (long)Nb * OH * OW;
@@ -1385,23 +1331,13 @@ void launch_conv_bwd_weight(const float* dy, const float* x, float* dw,
   dim3 grid((Kout + 63) / 64, (Ncrs + BN - 1) / BN, SK);
   hipStream_t st = (hipStream_t)s;
   if (conv_bwdw_small(Kout, Ncrs)) {
-    // one 128-row tile per block where possible: 512 fixed chunks left the
-    // chip at 2 blocks/CU (48 KB LDS, 4 waves) — finer chunking trades a
-    // longer fixed-order reduce for 3x the resident parallelism
-    int chunks = (int)min((Kdim + 127) / 128, (long)kSmallBwdwMaxChunks);
-    if (chunks < 64) chunks = 64;
+    int chunks = conv_small_bwdw_chunks(Kdim);
     long kpc = ((Kdim + chunks - 1) / chunks + 127) / 128 * 128;
     conv_small_bwdw_k<128><<<chunks, 256, 0, st>>>(dy, x, ws, sh, Ncrs,
                                                    kpc);
-    int pairs = Kout * Ncrs;
-    int wpb = kBlock / kWave;
-    conv_small_bwdw_reduce_k<<<(pairs + wpb - 1) / wpb, kBlock, 0, st>>>(
-        ws, dw, Kout, C, R * S, chunks);
     return;
   }
-  float* slabs = ws;                         // SK * Kout * Ncrs
-  float* rsc = ws + (long)SK * Kout * Ncrs;  // Kout * Ncrs, rsc order
-  float* target = SK == 1 ? rsc : slabs;
+  float* target = conv_bwdw_target(ws, SK, Kout, Ncrs);
   bool v4 = (C % 4) == 0;
   if (pad == 0 && v4)
     conv_bwd_weight_k<true, true><<<grid, 256, 0, st>>>(
@@ -1415,9 +1351,91 @@ void launch_conv_bwd_weight(const float* dy, const float* x, float* dw,
   else
     conv_bwd_weight_k<false, false><<<grid, 256, 0, st>>>(
         dy, x, target, sh, Ncrs, k_per_chunk, SK == 1);
+}
+
+static StepRole conv_small_bwdw_reduce_role(const float* partials, float* dw,
+                                            int KO, int C, int RS,
+                                            int chunks) {
+  int pairs = KO * C * RS;
+  int wpb = kBlock / kWave;
+  StepRole r{};
+  r.kind = kRoleConvSmallBwdwReduce;
+  r.gx = (pairs + wpb - 1) / wpb;
+  r.gy = 1;
+  r.count = r.gx;
+  r.p[0] = partials; r.p[1] = dw;
+  r.i[0] = KO; r.i[1] = C; r.i[2] = RS; r.i[3] = chunks;
+  return r;
+}
+
+static StepRole splitk_reduce_dwperm_role(const float* ws, float* dw,
+                                          int Kout, int C, int RS, int SK) {
+  StepRole r{};
+  r.kind = kRoleSplitkReduceDwperm;
+  r.gx = grid_for((long)Kout * C * RS);
+  r.gy = 1;
+  r.count = r.gx;
+  r.p[0] = ws; r.p[1] = dw;
+  r.i[0] = Kout; r.i[1] = C; r.i[2] = RS; r.i[3] = SK;
+  return r;
+}
+
+// launch_splitk_reduce_dwperm as roles: returns the number of levels, 1
+// (*l1 is the whole combine) or 2 (*l1 folds, then *l2 finishes).
+int splitk_reduce_dwperm_roles(const float* ws, float* dw, int Kout, int C,
+                               int RS, int SK, StepRole* l1, StepRole* l2) {
+  long n_out = (long)Kout * C * RS;
+  if (SK > kSplitKFold) {
+    int chunks = splitk_stage1_slabs(SK);
+    float* ws2 = const_cast<float*>(ws) + (long)(SK + 1) * n_out;
+    *l1 = splitk_partial_role(ws, ws2, n_out, SK, kSplitKFold);
+    *l2 = splitk_reduce_dwperm_role(ws2, dw, Kout, C, RS, chunks);
+    return 2;
+  }
+  *l1 = splitk_reduce_dwperm_role(ws, dw, Kout, C, RS, SK);
+  return 1;
+}
+
+// The combine of launch_conv_bwd_weight as roles over the ws its main
+// kernels filled; levels as splitk_reduce_dwperm_roles.
+int conv_bwd_weight_combine_roles(float* ws, float* dw, int SK, int Nb,
+                                  int C, int Kout, int R, int S, int OH,
+                                  int OW, StepRole* l1, StepRole* l2) {
+  int Ncrs = C * R * S;
+  if (conv_bwdw_small(Kout, Ncrs)) {
+    *l1 = conv_small_bwdw_reduce_role(
+        ws, dw, Kout, C, R * S, conv_small_bwdw_chunks((long)Nb * OH * OW));
+    return 1;
+  }
+  return splitk_reduce_dwperm_roles(conv_bwdw_target(ws, SK, Kout, Ncrs), dw,
+                                    Kout, C, R * S, SK, l1, l2);
+}
+
+void launch_conv_small_bwdw_reduce(const float* partials, float* dw, int KO,
+                                   int C, int RS, int chunks, void* s) {
+  StepRole r = conv_small_bwdw_reduce_role(partials, dw, KO, C, RS, chunks);
+  conv_small_bwdw_reduce_k<<<r.gx, kBlock, 0, (hipStream_t)s>>>(
+      partials, dw, KO, C, RS, chunks);
+}
+
+// ws: conv_bwd_weight_ws_floats(Kout, Ncrs, SK) floats
+void launch_conv_bwd_weight(const float* dy, const float* x, float* dw,
+                            float* ws, int SK, int Nb, int C, int H, int W,
+                            int Kout, int R, int S, int OH, int OW,
+                            int stride, int pad, void* s) {
+  launch_conv_bwd_weight_main(dy, x, ws, SK, Nb, C, H, W, Kout, R, S, OH, OW,
+                              stride, pad, s);
+  int Ncrs = C * R * S;
+  if (conv_bwdw_small(Kout, Ncrs)) {
+    launch_conv_small_bwdw_reduce(ws, dw, Kout, C, R * S,
+                                  conv_small_bwdw_chunks((long)Nb * OH * OW),
+                                  s);
+    return;
+  }
   // fused combine+permute (for SK==1 it degenerates to the permute of
   // the directly-written rsc tensor)
-  launch_splitk_reduce_dwperm(target, dw, Kout, C, R * S, SK, s);
+  launch_splitk_reduce_dwperm(conv_bwdw_target(ws, SK, Kout, Ncrs), dw, Kout,
+                              C, R * S, SK, s);
 }
 
 constexpr int kConvDbMaxChunks = 4096;
@@ -1440,17 +1458,40 @@ static int conv_db_kblk(int Kout) {
   return (kBlock % Kout == 0) ? Kout : kBlock;
 }
 
-void launch_conv_db(const float* dy, float* db, float* partials, int Nb,
-                    int Kout, int OHW, void* s) {
-  hipStream_t st = (hipStream_t)s;
+// launch_conv_db as roles: *l1 the chunk partials, *l2 their fold
+void conv_db_roles(const float* dy, float* db, float* partials, int Nb,
+                   int Kout, int OHW, StepRole* l1, StepRole* l2) {
   long M = (long)Nb * OHW;
   int chunks = conv_db_chunks(M, Kout);
   int K_blk = conv_db_kblk(Kout);
   int sub_per = kBlock / K_blk;
-  dim3 g1((chunks + sub_per - 1) / sub_per, (Kout + K_blk - 1) / K_blk);
-  conv_db_stage1_k<<<g1, kBlock, 0, st>>>(dy, partials, M, Kout, chunks,
-                                          K_blk);
-  conv_db_stage2_k<<<Kout, kBlock, 0, st>>>(partials, db, Kout, chunks);
+  StepRole a{};
+  a.kind = kRoleConvDbStage1;
+  a.gx = (chunks + sub_per - 1) / sub_per;
+  a.gy = (Kout + K_blk - 1) / K_blk;
+  a.count = a.gx * a.gy;
+  a.p[0] = dy; a.p[1] = partials;
+  a.l0 = M;
+  a.i[0] = Kout; a.i[1] = chunks; a.i[2] = K_blk;
+  *l1 = a;
+  StepRole b{};
+  b.kind = kRoleConvDbStage2;
+  b.gx = Kout;
+  b.gy = 1;
+  b.count = Kout;
+  b.p[0] = partials; b.p[1] = db;
+  b.i[0] = Kout; b.i[1] = chunks;
+  *l2 = b;
+}
+
+void launch_conv_db(const float* dy, float* db, float* partials, int Nb,
+                    int Kout, int OHW, void* s) {
+  hipStream_t st = (hipStream_t)s;
+  StepRole a, b;
+  conv_db_roles(dy, db, partials, Nb, Kout, OHW, &a, &b);
+  conv_db_stage1_k<<<dim3(a.gx, a.gy), kBlock, 0, st>>>(
+      dy, partials, a.l0, Kout, a.i[1], a.i[2]);
+  conv_db_stage2_k<<<b.gx, kBlock, 0, st>>>(partials, db, Kout, b.i[1]);
 }
 
 // The conv backward-weight split-K workspace, fp32 and bf16: SK slabs of
@@ -1464,17 +1505,16 @@ long conv_dwperm_ws_floats(int Kout, int Ncrs, int SK) {
 // its rsc temp when SK == 1
 void launch_splitk_reduce_dwperm(const float* ws, float* dw, int Kout,
                                  int C, int RS, int SK, void* s) {
-  long n_out = (long)Kout * C * RS;
-  if (SK > kSplitKFold) {  // fold into the stage-1 slabs after slabs + rsc
-    int chunks = splitk_stage1_slabs(SK);
-    float* ws2 = const_cast<float*>(ws) + (long)(SK + 1) * n_out;
-    launch_splitk_partial(ws, ws2, n_out, SK, kSplitKFold, s);
-    splitk_reduce_dwperm_k<<<grid_for(n_out), kBlock, 0, (hipStream_t)s>>>(
-        ws2, dw, Kout, C, RS, chunks);
-    return;
+  // predicate, grids and the stage-1 offset live in
+  // splitk_reduce_dwperm_roles, shared with the queued path
+  StepRole a, b;
+  if (splitk_reduce_dwperm_roles(ws, dw, Kout, C, RS, SK, &a, &b) == 2) {
+    launch_splitk_partial((const float*)a.p[0], (float*)a.p[1], a.l0, a.i[0],
+                          a.i[1], s);
+    a = b;
   }
-  splitk_reduce_dwperm_k<<<grid_for(n_out), kBlock, 0, (hipStream_t)s>>>(
-      ws, dw, Kout, C, RS, SK);
+  splitk_reduce_dwperm_k<<<a.gx, kBlock, 0, (hipStream_t)s>>>(
+      (const float*)a.p[0], dw, Kout, C, RS, a.i[3]);
 }
 
 void launch_dwperm_rsc_crs(const float* in, float* out, int Kout, int C,
@@ -1489,14 +1529,28 @@ void launch_conv_db_stage2(const float* partials, float* db, int Kout,
                                                         chunks);
 }
 
+// the two weight permutes as roles (kind: 0 = launch_wperm_crs_ko, the
+// forward's wt; 1 = launch_wperm_kors_c, bwd-data's wp)
+StepRole wperm_role(int kind, const float* w, float* out, int Kout, int C,
+                    int RS) {
+  StepRole r{};
+  r.kind = kind == 0 ? kRoleWpermRscKo : kRoleWpermRskoC;
+  r.gx = grid_for((long)Kout * C * RS);
+  r.gy = 1;
+  r.count = r.gx;
+  r.p[0] = w; r.p[1] = out;
+  r.i[0] = Kout; r.i[1] = C; r.i[2] = RS;
+  return r;
+}
+
 void launch_wperm_crs_ko(const float* w, float* out, int Kout, int C, int RS,
                          void* s) {
-  wperm_rsc_ko_k<<<grid_for((long)Kout * C * RS), kBlock, 0,
+  wperm_rsc_ko_k<<<wperm_role(0, w, out, Kout, C, RS).gx, kBlock, 0,
                    (hipStream_t)s>>>(w, out, Kout, C, RS);
 }
 void launch_wperm_kors_c(const float* w, float* out, int Kout, int C, int RS,
                          void* s) {
-  wperm_rsko_c_k<<<grid_for((long)Kout * C * RS), kBlock, 0,
+  wperm_rsko_c_k<<<wperm_role(1, w, out, Kout, C, RS).gx, kBlock, 0,
                    (hipStream_t)s>>>(w, out, Kout, C, RS);
 }
 }

@@ -2,8 +2,9 @@
 // The reference runs clip_grad_norm_ + SGD.step + an optional full
 // pack/norm/unpack PGD projection per BATCH (agent.py:50-60).  On flat
 // buffers that whole sequence is two reductions + two updates; reductions
-// are two-stage (block partials -> single-block finalize) for run-to-run
-// determinism (no float atomics).
+// are two-stage (block partials -> one fixed tree over them, which every
+// block of the update kernel repeats) for run-to-run determinism (no float
+// atomics).
 #include "common.h"
 #include "launchers.h"
 
@@ -31,37 +32,43 @@ __global__ void sq_partials_k(const float* __restrict__ a,
 }
 
 // ---- stage 2: finalize the scalar the update kernels consume ----
-// mode 0 (sgd clip):  out = min(1, max_norm / (||g|| + 1e-6))
-// mode 1 (pgd):       out = 1 / max(1, ||u|| / clip)
-__global__ void finalize_scale_k(const float* __restrict__ partials,
-                                 float* __restrict__ out, int nb, float c,
-                                 int mode) {
-  __shared__ float sh[kNPart];
-  float acc = (threadIdx.x < nb) ? partials[threadIdx.x] : 0.f;
-  sh[threadIdx.x] = acc;
+// mode 0 (sgd clip):  min(1, max_norm / (||g|| + 1e-6))
+// mode 1 (pgd):       1 / max(1, ||u|| / clip)
+// The tree over the kNPart partials, by a block of any width that divides
+// kNPart: level `off` adds sh[i + off] into sh[i] for every i < off, the
+// levels separated by barriers, so the pairing (and the sum, bitwise) is
+// the same for every block width.  sh: kNPart floats; all threads return
+// the scale.
+__device__ __forceinline__ float finalize_scale_block(
+    const float* __restrict__ partials, int nb, float c, int mode,
+    float* sh) {
+  for (int i = threadIdx.x; i < kNPart; i += blockDim.x)
+    sh[i] = (i < nb) ? partials[i] : 0.f;
   __syncthreads();
   for (int off = kNPart / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off) sh[threadIdx.x] += sh[threadIdx.x + off];
+    for (int i = threadIdx.x; i < off; i += blockDim.x) sh[i] += sh[i + off];
     __syncthreads();
   }
-  if (threadIdx.x == 0) {
-    float norm = sqrtf(sh[0]);
-    if (mode == 0) {
-      float coef = c / (norm + 1e-6f);
-      out[0] = coef < 1.f ? coef : 1.f;
-    } else {
-      float denom = norm / c;
-      out[0] = denom > 1.f ? 1.f / denom : 1.f;
-    }
+  float norm = sqrtf(sh[0]);
+  if (mode == 0) {
+    float coef = c / (norm + 1e-6f);
+    return coef < 1.f ? coef : 1.f;
   }
+  float denom = norm / c;
+  return denom > 1.f ? 1.f / denom : 1.f;
 }
 
 // ---- v = mu*v + g*scale ; p -= lr*v ----
+// Every block finalizes the clip scale itself from the kNPart partials
+// (mode 0, c = max_norm): the same tree in every block, so the same bits,
+// and one launch fewer than a single-block finalize kernel in between
+// (5.0 + 4.7 us -> 6.8 us traced, profiles/step_batch_after.md).
 __global__ void sgd_update_k(float* __restrict__ p, const float* __restrict__ g,
                              float* __restrict__ v,
-                             const float* __restrict__ scale, float lr,
-                             float mu, long n) {
-  float s = scale[0];
+                             const float* __restrict__ partials, float lr,
+                             float mu, long n, float c) {
+  __shared__ float sh[kNPart];
+  float s = finalize_scale_block(partials, kNPart, c, 0, sh);
   long stride = (long)gridDim.x * blockDim.x;
   long n4 = n / 4;
   long i4 = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -84,10 +91,13 @@ __global__ void sgd_update_k(float* __restrict__ p, const float* __restrict__ g,
 }
 
 // ---- p = t0 + (p - t0) * scale  (PGD projection apply) ----
+// (scale finalized per block as in sgd_update_k: mode 1, c = clip)
 __global__ void pgd_apply_k(float* __restrict__ p,
                             const float* __restrict__ t0,
-                            const float* __restrict__ scale, long n) {
-  float s = scale[0];
+                            const float* __restrict__ partials, long n,
+                            float c) {
+  __shared__ float sh[kNPart];
+  float s = finalize_scale_block(partials, kNPart, c, 1, sh);
   long stride = (long)gridDim.x * blockDim.x;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
        i += stride)
@@ -105,27 +115,23 @@ __global__ void delta64_k(const float* __restrict__ p,
 }
 
 extern "C" {
-// scratch of launch_clipped_sgd and launch_pgd_project: kNPart partials,
-// then the one scale the update kernel reads
+// scratch of launch_clipped_sgd and launch_pgd_project: kNPart partials
+// (and one float that held the finalized scale while a kernel of its own
+// wrote it; the size stays as callers and tests pin it)
 long flat_norm_scratch_floats() { return kNPart + 1; }
 
 void launch_clipped_sgd(float* p, const float* g, float* v, float* scratch,
                         float lr, float mu, float max_norm, long n, void* s) {
   hipStream_t st = (hipStream_t)s;
   sq_partials_k<<<kNPart, kBlock, 0, st>>>(g, nullptr, scratch, n);
-  finalize_scale_k<<<1, kNPart, 0, st>>>(scratch, scratch + kNPart, kNPart,
-                                         max_norm, 0);
-  sgd_update_k<<<grid_for(n / 4 + 1), kBlock, 0, st>>>(p, g, v,
-                                                       scratch + kNPart, lr,
-                                                       mu, n);
+  sgd_update_k<<<grid_for(n / 4 + 1), kBlock, 0, st>>>(p, g, v, scratch, lr,
+                                                       mu, n, max_norm);
 }
 void launch_pgd_project(float* p, const float* t0, float* scratch, float clip,
                         long n, void* s) {
   hipStream_t st = (hipStream_t)s;
   sq_partials_k<<<kNPart, kBlock, 0, st>>>(p, t0, scratch, n);
-  finalize_scale_k<<<1, kNPart, 0, st>>>(scratch, scratch + kNPart, kNPart,
-                                         clip, 1);
-  pgd_apply_k<<<grid_for(n), kBlock, 0, st>>>(p, t0, scratch + kNPart, n);
+  pgd_apply_k<<<grid_for(n), kBlock, 0, st>>>(p, t0, scratch, n, clip);
 }
 void launch_delta64(const float* p, const double* t0, double* out, long n,
                     void* s) {

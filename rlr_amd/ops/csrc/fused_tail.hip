@@ -15,6 +15,7 @@
 // rounded to a float is still one float here.  No atomics, no grid sync.
 #include "common.h"
 #include "launchers.h"
+#include "step_roles.h"
 #include "tail_math.h"
 
 // ============================================================ the seam
@@ -305,37 +306,8 @@ void fc_head_reduce_k(const float* __restrict__ gl,
                       float* __restrict__ loss, int B, int H, int C,
                       int dw_blocks, int db_blocks, int dw_wave) {
   __shared__ float sh[kBlock];
-  const int blk = blockIdx.x;
-  const int wave = threadIdx.x / kWave, lane = threadIdx.x % kWave;
-  const long n_out = (long)C * H;
-  if (blk < dw_blocks) {
-    long out = dw_wave ? blk * (long)(kBlock / kWave) + wave
-                       : blk * (long)kBlock + threadIdx.x;
-    if (out >= n_out) return;
-    int n = (int)(out % H);
-    int m = (int)(out / H);
-    const float* a = gl + m;
-    const float* bp = d2 + n;
-    if (dw_wave) {
-      float acc = dot_wave_partial(
-          B, lane, [&](int k) { return a[(long)k * C]; },
-          [&](int k) { return bp[(long)k * H]; });
-      acc = wave_tree_down(acc);
-      if (lane == 0) dw[(long)m * H + n] = acc;
-    } else {
-      dw[(long)m * H + n] =
-          dot_rot4(B, [&](int k) { return a[(long)k * C]; },
-                   [&](int k) { return bp[(long)k * H]; });
-    }
-  } else if (blk < dw_blocks + db_blocks) {
-    int n = (blk - dw_blocks) * (kBlock / kWave) + wave;
-    if (n >= C) return;
-    float acc = colsum_wave(gl, B, C, n, lane);
-    if (lane == 0) db[n] = acc;
-  } else {
-    float mean = ce_mean_block(row_loss, B, sh);
-    if (threadIdx.x == 0) loss[0] = mean;
-  }
+  fc_head_reduce_body(blockIdx.x, gl, d2, row_loss, dw, db, loss, B, H, C,
+                      dw_blocks, db_blocks, dw_wave, sh);
 }
 
 // launch_gemm_f32's tiny-problem branch and its thread / wave choice
@@ -384,27 +356,57 @@ long fc_head_ws_floats(int B, int H, int C) {
   return (long)B * H + (long)B * C + B;
 }
 
+// stage A: per-row work, into ws (dropped activations, dlogits, row
+// losses) and g_h1
+void launch_fc_head_rows(const float* h1, const float* w, const float* bias,
+                         const long* labels, const float* dloss, float* ws,
+                         float* g_h1, int B, int H, int C, float p,
+                         const unsigned long long* state, int site,
+                         void* s) {
+  float* d2 = ws;
+  float* gl = d2 + (long)B * H;
+  float* row_loss = gl + (long)B * C;
+  const int wpb = kBlock / kWave;
+  fc_head_rows_k<<<(B + wpb - 1) / wpb, kBlock, 0, (hipStream_t)s>>>(
+      h1, w, bias, labels, dloss, d2, gl, row_loss, g_h1, B, H, C, p, state,
+      site, H >= 32, C >= 32);
+}
+
+// stage B as a role over the ws that stage A filled
+StepRole fc_head_reduce_role(const float* ws, float* dw, float* db,
+                             float* loss, int B, int H, int C) {
+  const float* d2 = ws;
+  const float* gl = d2 + (long)B * H;
+  const float* row_loss = gl + (long)B * C;
+  const int wpb = kBlock / kWave;
+  const int dw_wave = B >= 32;
+  const long n_out = (long)C * H;
+  const int dw_blocks = (int)(dw_wave ? (n_out + wpb - 1) / wpb
+                                      : (n_out + kBlock - 1) / kBlock);
+  const int db_blocks = (C + wpb - 1) / wpb;
+  StepRole r{};
+  r.kind = kRoleFcHeadReduce;
+  r.gx = dw_blocks + db_blocks + 1;
+  r.gy = 1;
+  r.count = r.gx;
+  r.p[0] = gl; r.p[1] = d2; r.p[2] = row_loss;
+  r.p[3] = dw; r.p[4] = db; r.p[5] = loss;
+  r.i[0] = B; r.i[1] = H; r.i[2] = C;
+  r.i[3] = dw_blocks; r.i[4] = db_blocks; r.i[5] = dw_wave;
+  return r;
+}
+
 void launch_fc_head_step(const float* h1, const float* w, const float* bias,
                          const long* labels, const float* dloss, float* ws,
                          float* g_h1, float* dw, float* db, float* loss,
                          int B, int H, int C, float p,
                          const unsigned long long* state, int site,
                          void* s) {
-  hipStream_t st = (hipStream_t)s;
-  float* d2 = ws;
-  float* gl = d2 + (long)B * H;
-  float* row_loss = gl + (long)B * C;
-  const int wpb = kBlock / kWave;
-  fc_head_rows_k<<<(B + wpb - 1) / wpb, kBlock, 0, st>>>(
-      h1, w, bias, labels, dloss, d2, gl, row_loss, g_h1, B, H, C, p, state,
-      site, H >= 32, C >= 32);
-  const int dw_wave = B >= 32;
-  const long n_out = (long)C * H;
-  const int dw_blocks = (int)(dw_wave ? (n_out + wpb - 1) / wpb
-                                      : (n_out + kBlock - 1) / kBlock);
-  const int db_blocks = (C + wpb - 1) / wpb;
-  fc_head_reduce_k<<<dw_blocks + db_blocks + 1, kBlock, 0, st>>>(
-      gl, d2, row_loss, dw, db, loss, B, H, C, dw_blocks, db_blocks,
-      dw_wave);
+  launch_fc_head_rows(h1, w, bias, labels, dloss, ws, g_h1, B, H, C, p, state,
+                      site, s);
+  StepRole r = fc_head_reduce_role(ws, dw, db, loss, B, H, C);
+  fc_head_reduce_k<<<r.gx, kBlock, 0, (hipStream_t)s>>>(
+      (const float*)r.p[0], (const float*)r.p[1], (const float*)r.p[2], dw,
+      db, loss, B, H, C, r.i[3], r.i[4], r.i[5]);
 }
 }

@@ -18,6 +18,7 @@
 // combines them.  No atomics anywhere: bitwise run-to-run reproducible.
 #include "common.h"
 #include "launchers.h"
+#include "step_roles.h"
 #include "tail_math.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -269,29 +270,12 @@ __global__ void splitk_reduce_wave_k(const float* __restrict__ ws,
   }
 }
 
+// (body: step_roles.h, shared with the role-batched launch)
 __global__ void splitk_reduce_k(const float* __restrict__ ws,
                                 float* __restrict__ C,
                                 const float* __restrict__ bias, int M, int N,
                                 int ldc, int SK, int relu) {
-  long n_out = (long)M * N;
-  long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_out;
-       i += stride) {
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int z = 0;
-    for (; z + 3 < SK; z += 4) {
-      a0 += ws[(long)z * n_out + i];
-      a1 += ws[(long)(z + 1) * n_out + i];
-      a2 += ws[(long)(z + 2) * n_out + i];
-      a3 += ws[(long)(z + 3) * n_out + i];
-    }
-    for (; z < SK; ++z) a0 += ws[(long)z * n_out + i];
-    float acc = (a0 + a1) + (a2 + a3);
-    int col = i % N;
-    if (bias) acc += bias[col];
-    if (relu) acc = fmaxf(acc, 0.f);
-    C[(i / N) * (long)ldc + col] = acc;
-  }
+  splitk_reduce_body(blockIdx.x, gridDim.x, ws, C, bias, M, N, ldc, SK, relu);
 }
 
 
@@ -358,11 +342,7 @@ __global__ void gemm_small_wave_k(const float* __restrict__ A,
 // columns, so each lane-step reads a coalesced-ish (64*N-strided) front.
 __global__ void colsum_k(const float* __restrict__ dY,
                          float* __restrict__ db, int M, int N) {
-  int n = blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
-  int lane = threadIdx.x % kWave;
-  if (n >= N) return;
-  float acc = colsum_wave(dY, M, N, n, lane);
-  if (lane == 0) db[n] = acc;
+  colsum_body(blockIdx.x, dY, db, M, N);
 }
 
 extern "C" {
@@ -396,10 +376,13 @@ long gemm_splitk_ws_floats(int M, int N, int SK) {
 
 // ws: null unless SK>1, then gemm_splitk_ws_floats(M, N, SK) floats.
 // layout: 0 = NN, 1 = A transposed ([K][M]), 2 = B transposed ([N][K]).
-void launch_gemm_f32(const float* A, const float* B, float* C,
-                     const float* bias, float* ws, int M, int N, int K,
-                     int lda, int ldb, int ldc, int SK, int relu,
-                     int layout, void* s) {
+// The main kernel only.  Returns 1 when it left SK partial slabs in ws that
+// launch_splitk_reduce (or the roles of splitk_reduce_roles) must still
+// fold into C, 0 when C is complete.
+int launch_gemm_f32_main(const float* A, const float* B, float* C,
+                         const float* bias, float* ws, int M, int N, int K,
+                         int lda, int ldb, int ldc, int SK, int relu,
+                         int layout, void* s) {
   hipStream_t st = (hipStream_t)s;
   // tiny problems: one direct kernel beats tile GEMM + split-K reduce;
   // with a real K give every output a wave (lane-strided K + shuffle)
@@ -412,7 +395,7 @@ void launch_gemm_f32(const float* A, const float* B, float* C,
       gemm_small_k<<<grid_for((long)M * N), kBlock, 0, st>>>(
           A, B, C, bias, M, N, K, lda, ldb, ldc, relu, layout);
     }
-    return;
+    return 0;
   }
   dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN, SK);
   long k_per_chunk = SK == 1 ? (long)K
@@ -445,7 +428,16 @@ void launch_gemm_f32(const float* A, const float* B, float* C,
     gemm_f32_k<false><<<grid, 256, 0, st>>>(A, B, out, bias, M, N, K, lda,
                                             ldb, ldc, k_per_chunk, relu,
                                             SK == 1);
-  if (SK > 1) launch_splitk_reduce(ws, C, bias, M, N, ldc, SK, relu, s);
+  return SK > 1;
+}
+
+void launch_gemm_f32(const float* A, const float* B, float* C,
+                     const float* bias, float* ws, int M, int N, int K,
+                     int lda, int ldb, int ldc, int SK, int relu,
+                     int layout, void* s) {
+  if (launch_gemm_f32_main(A, B, C, bias, ws, M, N, K, lda, ldb, ldc, SK,
+                           relu, layout, s))
+    launch_splitk_reduce(ws, C, bias, M, N, ldc, SK, relu, s);
 }
 
 // stage-1 partial for deep split-K: each (output, 16-slab chunk) gets its
@@ -454,61 +446,103 @@ void launch_gemm_f32(const float* A, const float* B, float* C,
 __global__ void splitk_partial_k(const float* __restrict__ ws,
                                  float* __restrict__ out, long n_out,
                                  int S, int zstride) {
-  long stride = (long)gridDim.x * blockDim.x;
-  long total = n_out * ((S + zstride - 1) / zstride);
-  for (long v = (long)blockIdx.x * blockDim.x + threadIdx.x; v < total;
-       v += stride) {
-    long i = v % n_out;
-    int chunk = (int)(v / n_out);
-    int z0 = chunk * zstride, z1 = min(S, z0 + zstride);
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-    int z = z0;
-    for (; z + 3 < z1; z += 4) {
-      a0 += ws[(long)z * n_out + i];
-      a1 += ws[(long)(z + 1) * n_out + i];
-      a2 += ws[(long)(z + 2) * n_out + i];
-      a3 += ws[(long)(z + 3) * n_out + i];
-    }
-    for (; z < z1; ++z) a0 += ws[(long)z * n_out + i];
-    out[(long)chunk * n_out + i] = (a0 + a1) + (a2 + a3);
+  splitk_partial_body(blockIdx.x, gridDim.x, ws, out, n_out, S, zstride);
+}
+
+StepRole splitk_partial_role(const float* ws, float* out, long n_out, int S,
+                             int zstride) {
+  int chunks = (S + zstride - 1) / zstride;
+  StepRole r{};
+  r.kind = kRoleSplitkPartial;
+  r.gx = grid_for(n_out * chunks);
+  r.gy = 1;
+  r.count = r.gx;
+  r.p[0] = ws; r.p[1] = out;
+  r.l0 = n_out;
+  r.i[0] = S; r.i[1] = zstride;
+  return r;
+}
+
+static StepRole splitk_reduce_role(const float* ws, float* C,
+                                   const float* bias, int M, int N, int ldc,
+                                   int SK, int relu) {
+  StepRole r{};
+  r.kind = kRoleSplitkReduce;
+  r.gx = grid_for((long)M * N);
+  r.gy = 1;
+  r.count = r.gx;
+  r.p[0] = ws; r.p[1] = C; r.p[2] = bias;
+  r.i[0] = M; r.i[1] = N; r.i[2] = ldc; r.i[3] = SK; r.i[4] = relu;
+  return r;
+}
+
+// launch_splitk_reduce as roles, by the same predicates: returns the
+// number of levels, 2 (*l1 folds, *l2 finishes), 1 (*l1 is the thread-form
+// reduce) or 0: the wave form has no role, the caller launches it.
+int splitk_reduce_roles(const float* ws, float* C, const float* bias, int M,
+                        int N, int ldc, int SK, int relu, StepRole* l1,
+                        StepRole* l2) {
+  long n_out = (long)M * N;
+  if (SK > kSplitKFold && n_out <= 262144) {
+    int chunks = splitk_stage1_slabs(SK);
+    float* ws2 = const_cast<float*>(ws) + (long)SK * n_out;
+    *l1 = splitk_partial_role(ws, ws2, n_out, SK, kSplitKFold);
+    *l2 = splitk_reduce_role(ws2, C, bias, M, N, ldc, chunks, relu);
+    return 2;
   }
+  if (n_out <= 8192 && SK >= 16) return 0;
+  *l1 = splitk_reduce_role(ws, C, bias, M, N, ldc, SK, relu);
+  return 1;
+}
+
+StepRole colsum_role(const float* dY, float* db, int M, int N) {
+  int wpb = kBlock / kWave;
+  StepRole r{};
+  r.kind = kRoleColsum;
+  r.gx = (N + wpb - 1) / wpb;
+  r.gy = 1;
+  r.count = r.gx;
+  r.p[0] = dY; r.p[1] = db;
+  r.i[0] = M; r.i[1] = N;
+  return r;
 }
 
 // ws holds gemm_splitk_ws_floats(M, N, SK) floats: the stage-1 scratch is
 // the splitk_stage1_slabs(SK) slabs after the SK partials
 void launch_splitk_reduce(const float* ws, float* C, const float* bias,
                           int M, int N, int ldc, int SK, int relu, void* s) {
-  long n_out = (long)M * N;
-  if (SK > kSplitKFold && n_out <= 262144) {
-    int chunks = splitk_stage1_slabs(SK);
-    float* ws2 = const_cast<float*>(ws) + (long)SK * n_out;
-    splitk_partial_k<<<grid_for(n_out * chunks), kBlock, 0,
-                       (hipStream_t)s>>>(ws, ws2, n_out, SK, kSplitKFold);
-    splitk_reduce_k<<<grid_for(n_out), kBlock, 0, (hipStream_t)s>>>(
-        ws2, C, bias, M, N, ldc, chunks, relu);
+  // the predicates, grids and ws offsets live in splitk_reduce_roles: the
+  // queued path and this one cannot drift apart
+  hipStream_t st = (hipStream_t)s;
+  StepRole a, b;
+  int levels = splitk_reduce_roles(ws, C, bias, M, N, ldc, SK, relu, &a, &b);
+  if (levels == 0) {
+    long n_out = (long)M * N;
+    int wpb = kBlock / kWave;
+    splitk_reduce_wave_k<<<(n_out + wpb - 1) / wpb, kBlock, 0, st>>>(
+        ws, C, bias, M, N, ldc, SK, relu);
     return;
   }
-  if (n_out <= 8192 && SK >= 16) {
-    int wpb = kBlock / kWave;
-    splitk_reduce_wave_k<<<(n_out + wpb - 1) / wpb, kBlock, 0,
-                           (hipStream_t)s>>>(ws, C, bias, M, N, ldc, SK,
-                                             relu);
-  } else {
-    splitk_reduce_k<<<grid_for(n_out), kBlock, 0, (hipStream_t)s>>>(
-        ws, C, bias, M, N, ldc, SK, relu);
+  if (levels == 2) {
+    splitk_partial_k<<<a.gx, kBlock, 0, st>>>(
+        (const float*)a.p[0], (float*)a.p[1], a.l0, a.i[0], a.i[1]);
+    a = b;
   }
+  splitk_reduce_k<<<a.gx, kBlock, 0, st>>>(
+      (const float*)a.p[0], (float*)a.p[1], (const float*)a.p[2], a.i[0],
+      a.i[1], a.i[2], a.i[3], a.i[4]);
 }
 
 
 void launch_splitk_partial(const float* ws, float* out, long n_out,
                            int S, int zstride, void* s) {
-  int chunks = (S + zstride - 1) / zstride;
-  splitk_partial_k<<<grid_for(n_out * chunks), kBlock, 0,
-                     (hipStream_t)s>>>(ws, out, n_out, S, zstride);
+  StepRole r = splitk_partial_role(ws, out, n_out, S, zstride);
+  splitk_partial_k<<<r.gx, kBlock, 0, (hipStream_t)s>>>(ws, out, n_out, S,
+                                                        zstride);
 }
 
 void launch_colsum(const float* dY, float* db, int M, int N, void* s) {
-  int wpb = kBlock / kWave;
-  colsum_k<<<(N + wpb - 1) / wpb, kBlock, 0, (hipStream_t)s>>>(dY, db, M, N);
+  StepRole r = colsum_role(dY, db, M, N);
+  colsum_k<<<r.gx, kBlock, 0, (hipStream_t)s>>>(dY, db, M, N);
 }
 }

@@ -8,7 +8,50 @@
 #pragma once
 #include <cstdint>
 
+// One entry of a role-batched launch (step_batch.hip): `count` consecutive
+// blocks starting at flat block `first` run the body `kind` as the blocks
+// of a virtual (gx, gy) grid, count == gx * gy.  p / l0 / i are the body's
+// pointers and integers in the order of its stand-alone kernel's arguments.
+// Each role maker below fills everything but `first`, which the launch
+// assigns (step_batch_plan).
+enum StepRoleKind {
+  kRoleConvDbStage1 = 0,
+  kRoleConvDbStage2,
+  kRoleSplitkPartial,
+  kRoleSplitkReduce,
+  kRoleSplitkReduceDwperm,
+  kRoleConvSmallBwdwReduce,
+  kRoleColsum,
+  kRoleFcHeadReduce,
+  kRoleWpermRscKo,
+  kRoleWpermRskoC,
+  kRoleGatherRows,
+  kRoleAddU64,
+};
+struct StepRole {
+  int kind;
+  int first;
+  int count;
+  int gx, gy;
+  int i[6];
+  long l0;
+  const void* p[6];
+};
+constexpr int kStepMaxRoles = 16;
+
 extern "C" {
+// step_batch.hip.  step_batch_plan: first[r] = blocks of the roles before
+// r, returns the total (host arithmetic only).  launch_step_batch runs up
+// to kStepMaxRoles roles in one launch (more: returns -1 and launches
+// nothing; 0 otherwise); roles with count == 0 are skipped, and nothing is
+// launched when every count is 0.
+int step_batch_max_roles();
+int step_batch_plan(const int* counts, int n, int* first);
+int step_batch_lookup(const int* counts, int n, int block, int* vblock);
+int launch_step_batch(const StepRole* roles, int n, void* s);
+StepRole step_role_gather_rows(const void* src, const long* sel, void* dst,
+                               long rows, int row_words, int src_rows);
+StepRole step_role_add_u64(unsigned long long* p, unsigned long long delta);
 // elementwise.hip
 void launch_relu_fwd(const float* x, float* y, long n, void* s);
 void launch_relu_bwd(const float* y, const float* dy, float* dx, long n,
@@ -120,6 +163,15 @@ void launch_fc_head_step(const float* h1, const float* w, const float* bias,
                          int B, int H, int C, float p,
                          const unsigned long long* state, int site,
                          void* s);
+// launch_fc_head_step's two stages apart: stage A launched, stage B as a
+// role of a batched launch over the same ws
+void launch_fc_head_rows(const float* h1, const float* w, const float* bias,
+                         const long* labels, const float* dloss, float* ws,
+                         float* g_h1, int B, int H, int C, float p,
+                         const unsigned long long* state, int site,
+                         void* s);
+StepRole fc_head_reduce_role(const float* ws, float* dw, float* db,
+                             float* loss, int B, int H, int C);
 // flatopt.hip
 long flat_norm_scratch_floats();
 void launch_clipped_sgd(float* p, const float* g, float* v, float* scratch,
@@ -175,6 +227,20 @@ void launch_gemm_f32(const float* A, const float* B, float* C,
                      int lda, int ldb, int ldc, int SK, int relu,
                      int layout, void* s);
 void launch_colsum(const float* dY, float* db, int M, int N, void* s);
+// launch_gemm_f32 without its split-K combine: returns 1 when ws holds SK
+// partial slabs that still have to be folded into C
+int launch_gemm_f32_main(const float* A, const float* B, float* C,
+                         const float* bias, float* ws, int M, int N, int K,
+                         int lda, int ldb, int ldc, int SK, int relu,
+                         int layout, void* s);
+// launch_splitk_reduce as roles: the number of levels filled, 0 when the
+// launcher would take its wave form (no role: launch it instead)
+int splitk_reduce_roles(const float* ws, float* C, const float* bias, int M,
+                        int N, int ldc, int SK, int relu, StepRole* l1,
+                        StepRole* l2);
+StepRole splitk_partial_role(const float* ws, float* out, long n_out, int S,
+                             int zstride);
+StepRole colsum_role(const float* dY, float* db, int M, int N);
 // gemm_bf16.hip
 void launch_gemm_bf16(const unsigned short* A, const unsigned short* B,
                       float* C, const float* bias, unsigned short* C16,
@@ -200,6 +266,23 @@ void launch_conv_bwd_weight(const float* dy, const float* x, float* dw,
                             float* ws, int SK, int Nb, int C, int H, int W,
                             int Kout, int R, int S, int OH, int OW,
                             int stride, int pad, void* s);
+// launch_conv_bwd_weight as main kernels + combine: the combine either
+// launched, or as roles (1 or 2 levels) over the ws the main kernels filled
+void launch_conv_bwd_weight_main(const float* dy, const float* x, float* ws,
+                                 int SK, int Nb, int C, int H, int W,
+                                 int Kout, int R, int S, int OH, int OW,
+                                 int stride, int pad, void* s);
+int conv_bwd_weight_combine_roles(float* ws, float* dw, int SK, int Nb,
+                                  int C, int Kout, int R, int S, int OH,
+                                  int OW, StepRole* l1, StepRole* l2);
+int splitk_reduce_dwperm_roles(const float* ws, float* dw, int Kout, int C,
+                               int RS, int SK, StepRole* l1, StepRole* l2);
+void launch_conv_small_bwdw_reduce(const float* partials, float* dw, int KO,
+                                   int C, int RS, int chunks, void* s);
+void conv_db_roles(const float* dy, float* db, float* partials, int Nb,
+                   int Kout, int OHW, StepRole* l1, StepRole* l2);
+StepRole wperm_role(int kind, const float* w, float* out, int Kout, int C,
+                    int RS);
 int conv_db_chunks(long M, int Kout);
 long conv_db_ws_floats(int Kout);
 void launch_conv_db(const float* dy, float* db, float* partials, int Nb,
