@@ -70,16 +70,23 @@ static unsigned short* bfp(const torch::Tensor& t) {
 }
 
 // ------------------------------------------------------------- step queue
-// The fp32 manual tape's deferred small kernels (step_batch.hip).  An entry
-// point that is handed a queue launches only its main kernels and pushes
-// its folds here as roles; flush() issues level 1 (every first stage and
-// every single-stage final) and then level 2 (the second stages) as
-// role-batched launches.  Roles of one level never depend on each other.
-// The queue keeps every tensor a pending role touches alive until flush.
+// The small fold / permute / copy kernels of the fp32 entry points, as
+// roles (step_batch.hip).  An entry point launches its main kernels and
+// pushes its roles here, level 1 (a first stage, or a single-stage final)
+// before level 2 (a second stage).  The deferred queue the manual tape
+// hands in keeps them, and every tensor they touch, until flush() issues
+// level 1 and then level 2 as role-batched launches; roles of one level
+// never depend on each other.  The immediate queue an entry point makes for
+// itself when it is handed none launches each role as it is pushed, on the
+// stream of the tensors just held, and keeps nothing: the caching allocator
+// already makes that safe, as for every other temporary here.
 struct StepQueue {
+  bool immediate;
   std::vector<StepRole> lv[2];
   std::vector<torch::Tensor> held;
   void* stream = nullptr;
+
+  explicit StepQueue(bool immediate_ = false) : immediate(immediate_) {}
 
   void hold(const torch::Tensor& t) {
     if (!t.defined()) return;
@@ -87,9 +94,15 @@ struct StepQueue {
     TORCH_CHECK(stream == nullptr || stream == st,
                 "StepQueue: roles of one flush must share a stream");
     stream = st;
-    held.push_back(t);
+    if (!immediate) held.push_back(t);
   }
-  void push(int level, const StepRole& r) { lv[level].push_back(r); }
+  void push(int level, const StepRole& r) {
+    if (!immediate) {
+      lv[level].push_back(r);
+      return;
+    }
+    TORCH_CHECK(launch_step_role(&r, stream) == 0, "StepQueue: bad role");
+  }
   std::tuple<int64_t, int64_t> pending() const {
     return {(int64_t)lv[0].size(), (int64_t)lv[1].size()};
   }
@@ -125,7 +138,7 @@ struct StepQueue {
     push(0, a);
     push(1, b);
   }
-  // launch_splitk_reduce_dwperm over ws (conv_dwperm_ws_floats layout)
+  // the split-K combine + dw permute over ws (conv_dwperm_ws_floats layout)
   void splitk_reduce_dwperm(torch::Tensor ws, torch::Tensor dw, int64_t Kout,
                             int64_t C, int64_t RS, int64_t SK,
                             int64_t ws_offset) {
@@ -138,8 +151,8 @@ struct StepQueue {
     push(0, a);
     if (levels == 2) push(1, b);
   }
-  // launch_splitk_reduce over ws; false (nothing queued) when the launcher
-  // would take its wave form, which has no role
+  // the split-K combine over ws; false (nothing pushed) for the wave form,
+  // which has no role: the caller runs launch_splitk_reduce
   bool splitk_reduce(torch::Tensor ws, torch::Tensor C,
                      c10::optional<torch::Tensor> bias, int64_t M, int64_t N,
                      int64_t ldc, int64_t SK, bool relu) {
@@ -161,7 +174,7 @@ struct StepQueue {
     push(0, colsum_role(f32c(dy), (float*)f32c(db_out), (int)dy.size(0),
                         (int)dy.size(1)));
   }
-  // the combine of launch_conv_bwd_weight over the ws its main kernels wrote
+  // the combine of backward-weight over the ws its main kernels wrote
   void conv_bwd_weight_combine(torch::Tensor ws, torch::Tensor dw, int SK,
                                int Nb, int C, int Kout, int R, int S, int OH,
                                int OW) {
@@ -179,6 +192,9 @@ struct StepQueue {
                               int64_t Nb, int64_t C, int64_t Kout, int64_t R,
                               int64_t S, int64_t OH, int64_t OW) {
     TORCH_CHECK(C * R * S <= 32 && Kout <= 64);
+    TORCH_CHECK(dw.is_contiguous() && dw.numel() == Kout * C * R * S);
+    TORCH_CHECK(partials.numel() >=
+                conv_small_bwdw_chunks(Nb * OH * OW) * Kout * C * R * S);
     conv_bwd_weight_combine(partials, dw, 1, (int)Nb, (int)C, (int)Kout,
                             (int)R, (int)S, (int)OH, (int)OW);
   }
@@ -747,18 +763,14 @@ static torch::Tensor gemm_f32(const torch::Tensor& A, const torch::Tensor& B,
     ws = torch::empty({gemm_splitk_ws_floats(M, N, SK)}, A.options());
   const float* bp = bias ? bias->data_ptr<float>() : nullptr;
   float* wsp = SK > 1 ? ws.data_ptr<float>() : nullptr;
-  if (!q) {
-    launch_gemm_f32(A.data_ptr<float>(), B.data_ptr<float>(),
-                    C.data_ptr<float>(), bp, wsp, M, N, K, lda, ldb, N, SK,
-                    relu ? 1 : 0, layout, stream_of(A));
-    return C;
-  }
-  // main kernel now; the split-K combine waits on the queue when the
-  // launcher's own predicates pick a form that has a role
+  StepQueue now(true);
+  StepQueue& sq = q ? *q : now;
+  // main kernel now; the split-K combine goes to the queue when its form
+  // has a role
   if (launch_gemm_f32_main(A.data_ptr<float>(), B.data_ptr<float>(),
                            C.data_ptr<float>(), bp, wsp, M, N, K, lda, ldb,
                            N, SK, relu ? 1 : 0, layout, stream_of(A)) &&
-      !q->splitk_reduce(ws, C, bias, M, N, N, SK, relu))
+      !sq.splitk_reduce(ws, C, bias, M, N, N, SK, relu))
     launch_splitk_reduce(wsp, C.data_ptr<float>(), bp, M, N, N, SK,
                          relu ? 1 : 0, stream_of(A));
   return C;
@@ -839,12 +851,8 @@ torch::Tensor linear_bwd_into(torch::Tensor x, torch::Tensor w,
     dx = gemm_f32(dy, w, c10::nullopt, false, bM, in, out, out, in, 0);
   gemm_f32(dy, x, c10::nullopt, false, out, in, bM, out, in, 1, dw_out, q);
   if (db_out) {
-    TORCH_CHECK(db_out->is_contiguous() && db_out->numel() == out);
-    if (q)
-      q->colsum(dy, *db_out);
-    else
-      launch_colsum(dy.data_ptr<float>(), db_out->data_ptr<float>(), bM, out,
-                  stream_of(dy));
+    StepQueue now(true);
+    (q ? *q : now).colsum(dy, *db_out);
   }
   return dx;
 }
@@ -963,26 +971,19 @@ std::tuple<torch::Tensor, torch::Tensor> fc_head_step(
   auto ws = torch::empty({fc_head_ws_floats(B, H, C)}, h1.options());
   auto g_h1 = torch::empty_like(h1);
   auto loss = torch::empty({}, h1.options());
-  if (q) {  // stage A now, stage B as a level-1 role
-    launch_fc_head_rows(h1.data_ptr<float>(), w.data_ptr<float>(),
-                        b.data_ptr<float>(), labels.data_ptr<int64_t>(),
-                        dl.data_ptr<float>(), ws.data_ptr<float>(),
-                        g_h1.data_ptr<float>(), B, H, C, (float)p,
-                        dropout_state(state), (int)site, stream_of(h1));
-    q->hold(ws); q->hold(dw_out); q->hold(db_out); q->hold(loss);
-    q->push(0, fc_head_reduce_role(ws.data_ptr<float>(),
-                                   dw_out.data_ptr<float>(),
-                                   db_out.data_ptr<float>(),
-                                   loss.data_ptr<float>(), B, H, C));
-    return {loss, g_h1};
-  }
-  launch_fc_head_step(h1.data_ptr<float>(), w.data_ptr<float>(),
+  // stage A now, stage B as a level-1 role
+  launch_fc_head_rows(h1.data_ptr<float>(), w.data_ptr<float>(),
                       b.data_ptr<float>(), labels.data_ptr<int64_t>(),
                       dl.data_ptr<float>(), ws.data_ptr<float>(),
-                      g_h1.data_ptr<float>(), dw_out.data_ptr<float>(),
-                      db_out.data_ptr<float>(), loss.data_ptr<float>(), B, H,
-                      C, (float)p, dropout_state(state), (int)site,
-                      stream_of(h1));
+                      g_h1.data_ptr<float>(), B, H, C, (float)p,
+                      dropout_state(state), (int)site, stream_of(h1));
+  StepQueue now(true);
+  StepQueue& sq = q ? *q : now;
+  sq.hold(ws); sq.hold(dw_out); sq.hold(db_out); sq.hold(loss);
+  sq.push(0, fc_head_reduce_role(ws.data_ptr<float>(),
+                                 dw_out.data_ptr<float>(),
+                                 db_out.data_ptr<float>(),
+                                 loss.data_ptr<float>(), B, H, C));
   return {loss, g_h1};
 }
 
@@ -1036,9 +1037,7 @@ torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w,
                 wt.scalar_type() == torch::kFloat &&
                 wt.numel() == w.numel());
   } else {
-    wt = torch::empty({(long)C * R * S, Kout}, w.options());
-    launch_wperm_crs_ko(w.data_ptr<float>(), wt.data_ptr<float>(), Kout, C,
-                        R * S, stream_of(x));
+    wt = StepQueue(true).wperm(w, 0);
   }
   auto y = empty_cl({Nb, Kout, OH, OW}, x.options());
   launch_conv_fwd(x.data_ptr<float>(), wt.data_ptr<float>(), bp,
@@ -1091,7 +1090,9 @@ static torch::Tensor conv_bwd_core(torch::Tensor x, torch::Tensor w,
                                    StepQueue* q = nullptr) {
   // wp_in (fp32): bwd-data's permuted weights, made once per step by the
   // caller (StepQueue::wperm kind 1).  q (fp32): the dw combine and the
-  // bias-gradient fold wait on the queue instead of launching here.
+  // bias-gradient fold wait on the queue instead of running here.
+  StepQueue now(true);
+  StepQueue& sq = q ? *q : now;
   TORCH_CHECK((!wp_in && !q) || !is_bf16(x),
               "pre-permuted weights and the step queue are fp32-only");
   x = cl(x, "conv_bwd.x");
@@ -1120,16 +1121,13 @@ static torch::Tensor conv_bwd_core(torch::Tensor x, torch::Tensor w,
       TORCH_CHECK(wp.is_cuda() && wp.is_contiguous() &&
                   wp.scalar_type() == torch::kFloat &&
                   wp.numel() == w.numel());
+    } else if (bf) {
+      wp = torch::empty({(long)Kout * R * S, C},
+                        w.options().dtype(torch::kBFloat16));
+      launch_wperm_rsko_c_bf16(w.data_ptr<float>(), bfp(wp), Kout, C, R * S,
+                               st);
     } else {
-      wp = torch::empty(
-          {(long)Kout * R * S, C},
-          bf ? w.options().dtype(torch::kBFloat16) : w.options());
-      if (bf)
-        launch_wperm_rsko_c_bf16(w.data_ptr<float>(), bfp(wp), Kout, C,
-                                 R * S, st);
-      else
-        launch_wperm_kors_c(w.data_ptr<float>(), wp.data_ptr<float>(), Kout,
-                            C, R * S, st);
+      wp = now.wperm(w, 1);  // bwd-data below reads it: never deferred
     }
     dx = empty_cl({Nb, C, H, W}, x.options());
     torch::Tensor ryt;
@@ -1166,32 +1164,21 @@ static torch::Tensor conv_bwd_core(torch::Tensor x, torch::Tensor w,
     int SK = conv_bwd_weight_splitk(Kout, Ncrs, Kdim);
     auto ws = torch::empty({conv_bwd_weight_ws_floats(Kout, Ncrs, SK)},
                            w.options());
-    if (q) {
-      launch_conv_bwd_weight_main(dy.data_ptr<float>(), x.data_ptr<float>(),
-                                  ws.data_ptr<float>(), SK, Nb, C, H, W,
-                                  Kout, R, S, OH, OW, st_, pd, st);
-      q->conv_bwd_weight_combine(ws, dw_out, SK, Nb, C, Kout, R, S, OH, OW);
-    } else {
-      launch_conv_bwd_weight(dy.data_ptr<float>(), x.data_ptr<float>(),
-                             dw_out.data_ptr<float>(), ws.data_ptr<float>(),
-                             SK, Nb, C, H, W, Kout, R, S, OH, OW, st_, pd,
-                             st);
-    }
+    launch_conv_bwd_weight_main(dy.data_ptr<float>(), x.data_ptr<float>(),
+                                ws.data_ptr<float>(), SK, Nb, C, H, W, Kout,
+                                R, S, OH, OW, st_, pd, st);
+    sq.conv_bwd_weight_combine(ws, dw_out, SK, Nb, C, Kout, R, S, OH, OW);
   }
 
   if (db_out) {
     TORCH_CHECK(db_out->is_contiguous() && db_out->numel() == Kout);
-    if (q) {
-      q->conv_db(dy, *db_out);
-      return dx;
-    }
-    auto parts = torch::empty({conv_db_ws_floats(Kout)}, w.options());
-    if (bf)
+    if (bf) {
+      auto parts = torch::empty({conv_db_ws_floats(Kout)}, w.options());
       launch_conv_db_bf16(bfc(dy), db_out->data_ptr<float>(),
                           parts.data_ptr<float>(), Nb, Kout, OH * OW, st);
-    else
-      launch_conv_db(dy.data_ptr<float>(), db_out->data_ptr<float>(),
-                     parts.data_ptr<float>(), Nb, Kout, OH * OW, st);
+    } else {
+      sq.conv_db(dy, *db_out);
+    }
   }
   return dx;
 }
@@ -1398,16 +1385,14 @@ void feed_gather(torch::Tensor X, torch::Tensor Y, torch::Tensor sel,
   q.flush();
 }
 
-// The stand-alone launchers of the batched roles, one binding each, so a
-// test can hold a role against the kernel it shares its body with.
+// Each role alone, one binding each, so a test can hold a role in a batch
+// against the same role run by itself: the output allocated here, the
+// StepQueue method of the same name on an immediate queue.
 torch::Tensor conv_db(torch::Tensor dy) {
   TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 && !is_bf16(dy));
   dy = cl(dy, "conv_db.dy");
-  int Nb = dy.size(0), Kout = dy.size(1), OHW = dy.size(2) * dy.size(3);
-  auto db = torch::empty({Kout}, dy.options());
-  auto parts = torch::empty({conv_db_ws_floats(Kout)}, dy.options());
-  launch_conv_db(dy.data_ptr<float>(), db.data_ptr<float>(),
-                 parts.data_ptr<float>(), Nb, Kout, OHW, stream_of(dy));
+  auto db = torch::empty({dy.size(1)}, dy.options());
+  StepQueue(true).conv_db(dy, db);
   return db;
 }
 
@@ -1416,9 +1401,7 @@ torch::Tensor splitk_reduce_dwperm(torch::Tensor ws, int64_t Kout, int64_t C,
   CHK_CUDA(ws);
   TORCH_CHECK(ws.numel() >= conv_dwperm_ws_floats(Kout, C * RS, SK));
   auto dw = torch::empty({Kout * C * RS}, ws.options());
-  launch_splitk_reduce_dwperm(ws.data_ptr<float>(), dw.data_ptr<float>(),
-                              (int)Kout, (int)C, (int)RS, (int)SK,
-                              stream_of(ws));
+  StepQueue(true).splitk_reduce_dwperm(ws, dw, Kout, C, RS, SK, 0);
   return dw;
 }
 
@@ -1427,49 +1410,34 @@ torch::Tensor splitk_reduce(torch::Tensor ws, int64_t M, int64_t N,
   CHK_CUDA(ws);
   TORCH_CHECK(ws.numel() >= gemm_splitk_ws_floats(M, N, SK));
   auto C = torch::empty({M, N}, ws.options());
-  launch_splitk_reduce(ws.data_ptr<float>(), C.data_ptr<float>(), nullptr,
-                       (int)M, (int)N, (int)N, (int)SK, 0, stream_of(ws));
+  if (!StepQueue(true).splitk_reduce(ws, C, c10::nullopt, M, N, N, SK, false))
+    launch_splitk_reduce(ws.data_ptr<float>(), C.data_ptr<float>(), nullptr,
+                         (int)M, (int)N, (int)N, (int)SK, 0, stream_of(ws));
   return C;
 }
 
-// chunk partials of a (C*R*S <= 32) layer's backward-weight -> dw, through
-// launch_conv_bwd_weight's own combine
+// chunk partials of a (C*R*S <= 32) layer's backward-weight -> dw
 torch::Tensor conv_small_bwdw_reduce(torch::Tensor partials, int64_t Nb,
                                      int64_t C, int64_t Kout, int64_t R,
                                      int64_t S, int64_t OH, int64_t OW) {
   CHK_CUDA(partials);
-  TORCH_CHECK(C * R * S <= 32 && Kout <= 64);
-  StepRole a, b;
   auto dw = torch::empty({Kout * C * R * S}, partials.options());
-  conv_bwd_weight_combine_roles(partials.data_ptr<float>(),
-                                dw.data_ptr<float>(), 1, (int)Nb, (int)C,
-                                (int)Kout, (int)R, (int)S, (int)OH, (int)OW,
-                                &a, &b);
-  TORCH_CHECK(partials.numel() >= (int64_t)a.i[3] * Kout * C * R * S);
-  launch_conv_small_bwdw_reduce(partials.data_ptr<float>(),
-                                dw.data_ptr<float>(), (int)Kout, (int)C,
-                                (int)(R * S), a.i[3], stream_of(partials));
+  StepQueue(true).conv_small_bwdw_reduce(partials, dw, Nb, C, Kout, R, S, OH,
+                                         OW);
   return dw;
 }
 
 torch::Tensor colsum(torch::Tensor dy) {
   CHK_CUDA(dy);
-  TORCH_CHECK(dy.dim() == 2 && dy.is_contiguous());
+  TORCH_CHECK(dy.dim() == 2);
   auto db = torch::empty({dy.size(1)}, dy.options());
-  launch_colsum(dy.data_ptr<float>(), db.data_ptr<float>(), (int)dy.size(0),
-                (int)dy.size(1), stream_of(dy));
+  StepQueue(true).colsum(dy, db);
   return db;
 }
 
 torch::Tensor wperm(torch::Tensor w, int64_t kind) {
-  TORCH_CHECK(w.is_cuda() && w.dim() == 4 && (kind == 0 || kind == 1));
-  w = w.contiguous();
-  int Kout = w.size(0), C = w.size(1), RS = w.size(2) * w.size(3);
-  auto out = kind == 0 ? torch::empty({(long)C * RS, Kout}, w.options())
-                       : torch::empty({(long)Kout * RS, C}, w.options());
-  (kind == 0 ? launch_wperm_crs_ko : launch_wperm_kors_c)(
-      w.data_ptr<float>(), out.data_ptr<float>(), Kout, C, RS, stream_of(w));
-  return out;
+  TORCH_CHECK(w.is_cuda());
+  return StepQueue(true).wperm(w, kind);
 }
 
 // (first block of each role, total blocks) of a batched launch
@@ -1593,8 +1561,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("state"), py::arg("site"), py::arg("dw_out"),
         py::arg("db_out"), py::arg("queue") = py::none());
   // step batching (step_batch.hip): the queue of deferred roles, the two
-  // one-launch helpers built on it, the stand-alone launcher of each role
-  // and the launch plan (host arithmetic only)
+  // one-launch helpers built on it, each role alone and the launch plan
+  // (host arithmetic only)
   py::class_<StepQueue>(m, "StepQueue")
       .def(py::init<>())
       .def("flush", &StepQueue::flush)

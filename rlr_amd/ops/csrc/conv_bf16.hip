@@ -562,7 +562,7 @@ __global__ void wperm_rsko_c_bf16_k(const float* __restrict__ w,
 }
 
 // bf16 NHWC conv-bias gradient: db[ko] = column sums of dy [M][KO]
-// (full-block slice mapping as in the f32 conv_db_stage1_k)
+// (full-block slice mapping as in the fp32 conv_db_stage1 role)
 __global__ void conv_db_bf16_stage1_k(const unsigned short* __restrict__ dy,
                                       float* __restrict__ partials, long M,
                                       int Kout, int chunks, int K_blk) {
@@ -632,15 +632,6 @@ void launch_conv_bwd_data_bf16_relu(const unsigned short* dy,
                                                   relu_y);
 }
 
-void launch_conv_bwd_data_bf16(const unsigned short* dy,
-                               const unsigned short* wp, unsigned short* dx,
-                               int Nb, int C, int H, int W, int Kout, int R,
-                               int S, int OH, int OW, int stride, int pad,
-                               void* s) {
-  launch_conv_bwd_data_bf16_relu(dy, wp, dx, nullptr, Nb, C, H, W, Kout, R,
-                                 S, OH, OW, stride, pad, s);
-}
-
 // variant 0: 64-wide tile depth-2; 1: 128-wide; 2: 64-wide depth-3 ring
 // ws: conv_dwperm_ws_floats(Kout, Ncrs, SK) floats (conv_f32.hip)
 void launch_conv_bwd_weight_bf16_ex(const unsigned short* dy,
@@ -682,7 +673,11 @@ void launch_conv_bwd_weight_bf16_ex(const unsigned short* dy,
       conv_bwd_weight_bf16_k<false, 64, 2><<<grid, 256, 0, st>>>(
           dy, x, target, sh, Ncrs, k_per_chunk, SK == 1);
   }
-  launch_splitk_reduce_dwperm(target, dw, Kout, C, R * S, SK, s);
+  StepRole a, b;
+  int levels =
+      splitk_reduce_dwperm_roles(target, dw, Kout, C, R * S, SK, &a, &b);
+  launch_step_role(&a, s);
+  if (levels == 2) launch_step_role(&b, s);
 }
 
 void launch_conv_bwd_weight_bf16(const unsigned short* dy,
@@ -711,15 +706,13 @@ void launch_wperm_rsko_c_bf16(const float* w, unsigned short* out, int Kout,
 void launch_conv_db_bf16(const unsigned short* dy, float* db,
                          float* partials, int Nb, int Kout, int OHW,
                          void* s) {
-  hipStream_t st = (hipStream_t)s;
-  long M = (long)Nb * OHW;
-  int chunks = conv_db_chunks(M, Kout);
-  int K_blk = Kout >= kBlock ? kBlock
-                             : ((kBlock % Kout == 0) ? Kout : kBlock);
-  int sub_per = kBlock / K_blk;
-  dim3 g1((chunks + sub_per - 1) / sub_per, (Kout + K_blk - 1) / K_blk);
-  conv_db_bf16_stage1_k<<<g1, kBlock, 0, st>>>(dy, partials, M, Kout,
-                                               chunks, K_blk);
-  launch_conv_db_stage2(partials, db, Kout, chunks, s);
+  // the fp32 plan (conv_db_roles) with a bf16 stage 1 on the same grid;
+  // stage 2 folds fp32 partials, so it is the fp32 role
+  StepRole a, b;
+  conv_db_roles(nullptr, db, partials, Nb, Kout, OHW, &a, &b);
+  const ConvDbStage1Args& p1 = a.conv_db_stage1;
+  conv_db_bf16_stage1_k<<<dim3(a.gx, a.gy), kBlock, 0, (hipStream_t)s>>>(
+      dy, partials, p1.M, p1.Kout, p1.chunks, p1.K_blk);
+  launch_step_role(&b, s);
 }
 }

@@ -20,7 +20,6 @@
 // wp[(r,s,ko)][c].  All reductions fixed-order; no atomics.
 #include "common.h"
 #include "launchers.h"
-#include "step_roles.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -1115,71 +1114,9 @@ void conv_small_bwdw_k(const float* __restrict__ dy,
     partials[(long)blockIdx.x * pairs + p] = acc[pi];
 }
 
-// combine partials (fixed order, wave per pair) + permute (r,s,c)->(c,r,s)
-// (body: step_roles.h, shared with the role-batched launch)
-__global__ void conv_small_bwdw_reduce_k(const float* __restrict__ partials,
-                                         float* __restrict__ dw, int KO,
-                                         int C, int RS, int chunks) {
-  conv_small_bwdw_reduce_body(blockIdx.x, partials, dw, KO, C, RS, chunks);
-}
-
-// fused split-K combine + dw permute: sums the SK rsc-ordered slabs and
-// writes straight into the torch (ko,(c,r,s)) layout — one kernel instead
-// of splitk_reduce + dwperm (the intermediate rsc tensor disappears)
-__global__ void splitk_reduce_dwperm_k(const float* __restrict__ ws,
-                                       float* __restrict__ dw, int Kout,
-                                       int C, int RS, int SK) {
-  splitk_reduce_dwperm_body(blockIdx.x, gridDim.x, ws, dw, Kout, C, RS, SK);
-}
-
-// dw column permute: [(ko)][(r,s,c)] -> torch layout [(ko)][(c,r,s)]
-__global__ void dwperm_rsc_crs_k(const float* __restrict__ in,
-                                 float* __restrict__ out, int Kout, int C,
-                                 int RS) {
-  long n = (long)Kout * C * RS;
-  long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride) {
-    int col = i % (C * RS);   // (r,s,c) flat
-    long ko = i / (C * RS);
-    int c = col % C;
-    int rs = col / C;
-    out[(ko * C + c) * RS + rs] = in[i];
-  }
-}
-
-// ---- conv bias gradient (NHWC): db[ko] = column sum of dy [M][KO] ----
-// Dynamic chunk count keeps >=64k threads busy regardless of Kout; stage 2
-// is one wave per ko over the chunk partials (shuffle tree, deterministic).
-// thread -> (slice = tid / K_blk, ko = tid % K_blk): all four waves of a
-// block work even when Kout < 256 (the one-slice form left 7/8 of each
-// block idle at Kout=32 — 21.5 us for a 9.4 MB column sum)
-__global__ void conv_db_stage1_k(const float* __restrict__ dy,
-                                 float* __restrict__ partials, long M,
-                                 int Kout, int chunks, int K_blk) {
-  conv_db_stage1_body(blockIdx.x, blockIdx.y, dy, partials, M, Kout, chunks,
-                      K_blk);
-}
-
-__global__ void conv_db_stage2_k(const float* __restrict__ partials,
-                                 float* __restrict__ db, int Kout,
-                                 int chunks) {
-  __shared__ float sh[kBlock];
-  conv_db_stage2_body(blockIdx.x, partials, db, Kout, chunks, sh);
-}
-
-// permute w (Kout,C,R,S) -> staged layouts
-__global__ void wperm_rsc_ko_k(const float* __restrict__ w,
-                               float* __restrict__ out, int Kout, int C,
-                               int RS) {
-  wperm_rsc_ko_body(blockIdx.x, gridDim.x, w, out, Kout, C, RS);
-}
-
-__global__ void wperm_rsko_c_k(const float* __restrict__ w,
-                               float* __restrict__ out, int Kout, int C,
-                               int RS) {
-  wperm_rsko_c_body(blockIdx.x, gridDim.x, w, out, Kout, C, RS);
-}
+// The folds and permutes around these kernels (the chunk and split-K
+// combines of backward-weight, the bias gradient, the weight permutes) are
+// roles: bodies in step_roles.h, makers below, run by step_batch.hip.
 
 extern "C" {
 void launch_conv_fwd(const float* x, const float* wt, const float* bias,
@@ -1266,14 +1203,6 @@ void launch_conv_bwd_data_relu(const float* dy, const float* wp,
     conv_bwd_data_k<0, false><<<grid, 256, 0, st>>>(dy, wp, dx, sh, Kdim, relu_y);
 }
 
-void launch_conv_bwd_data(const float* dy, const float* wp, float* dx,
-                          int Nb, int C, int H, int W, int Kout, int R,
-                          int S, int OH, int OW, int stride, int pad,
-                          void* s) {
-  launch_conv_bwd_data_relu(dy, wp, dx, nullptr, Nb, C, H, W, Kout, R, S,
-                            OH, OW, stride, pad, s);
-}
-
 int conv_bwd_weight_splitk(int Kout, int Ncrs, long Kdim) {
   long tiles = ((Kout + 63) / 64) * (long)((Ncrs + BN - 1) / BN);
   if (tiles >= 2304 || Kdim <= 2 * BK) return 1;
@@ -1305,7 +1234,7 @@ long conv_bwd_weight_ws_floats(int Kout, int Ncrs, int SK) {
 // one 128-row tile per block where possible: 512 fixed chunks left the
 // chip at 2 blocks/CU (48 KB LDS, 4 waves) — finer chunking trades a
 // longer fixed-order reduce for 3x the resident parallelism
-static int conv_small_bwdw_chunks(long Kdim) {
+int conv_small_bwdw_chunks(long Kdim) {
   int chunks = (int)min((Kdim + 127) / 128, (long)kSmallBwdwMaxChunks);
   return chunks < 64 ? 64 : chunks;
 }
@@ -1317,8 +1246,7 @@ static float* conv_bwdw_target(float* ws, int SK, int Kout, int Ncrs) {
 }
 
 // The main kernels only: chunk partials (small path) or split-K slabs into
-// ws.  launch_conv_bwd_weight_combine, or the roles of
-// conv_bwd_weight_combine_roles, finish dw from them.
+// ws.  The roles of conv_bwd_weight_combine_roles finish dw from them.
 void launch_conv_bwd_weight_main(const float* dy, const float* x, float* ws,
                                  int SK, int Nb, int C, int H, int W,
                                  int Kout, int R, int S, int OH, int OW,
@@ -1363,8 +1291,12 @@ static StepRole conv_small_bwdw_reduce_role(const float* partials, float* dw,
   r.gx = (pairs + wpb - 1) / wpb;
   r.gy = 1;
   r.count = r.gx;
-  r.p[0] = partials; r.p[1] = dw;
-  r.i[0] = KO; r.i[1] = C; r.i[2] = RS; r.i[3] = chunks;
+  r.conv_small_bwdw_reduce.partials = partials;
+  r.conv_small_bwdw_reduce.dw = dw;
+  r.conv_small_bwdw_reduce.KO = KO;
+  r.conv_small_bwdw_reduce.C = C;
+  r.conv_small_bwdw_reduce.RS = RS;
+  r.conv_small_bwdw_reduce.chunks = chunks;
   return r;
 }
 
@@ -1375,13 +1307,21 @@ static StepRole splitk_reduce_dwperm_role(const float* ws, float* dw,
   r.gx = grid_for((long)Kout * C * RS);
   r.gy = 1;
   r.count = r.gx;
-  r.p[0] = ws; r.p[1] = dw;
-  r.i[0] = Kout; r.i[1] = C; r.i[2] = RS; r.i[3] = SK;
+  r.splitk_reduce_dwperm.ws = ws;
+  r.splitk_reduce_dwperm.dw = dw;
+  r.splitk_reduce_dwperm.Kout = Kout;
+  r.splitk_reduce_dwperm.C = C;
+  r.splitk_reduce_dwperm.RS = RS;
+  r.splitk_reduce_dwperm.SK = SK;
   return r;
 }
 
-// launch_splitk_reduce_dwperm as roles: returns the number of levels, 1
-// (*l1 is the whole combine) or 2 (*l1 folds, then *l2 finishes).
+// The fused split-K combine + dw permute: sums the SK rsc-ordered slabs and
+// writes straight into the torch (ko,(c,r,s)) layout (for SK == 1 it is the
+// permute of the directly-written rsc tensor).  Returns the number of
+// levels, 1 (*l1 is the whole combine) or 2 (*l1 folds, then *l2 finishes).
+// ws: the first slab of a conv_dwperm_ws_floats workspace when SK > 1, its
+// rsc temp when SK == 1.
 int splitk_reduce_dwperm_roles(const float* ws, float* dw, int Kout, int C,
                                int RS, int SK, StepRole* l1, StepRole* l2) {
   long n_out = (long)Kout * C * RS;
@@ -1396,8 +1336,8 @@ int splitk_reduce_dwperm_roles(const float* ws, float* dw, int Kout, int C,
   return 1;
 }
 
-// The combine of launch_conv_bwd_weight as roles over the ws its main
-// kernels filled; levels as splitk_reduce_dwperm_roles.
+// The combine of backward-weight as roles over the ws the main kernels
+// filled; levels as splitk_reduce_dwperm_roles.
 int conv_bwd_weight_combine_roles(float* ws, float* dw, int SK, int Nb,
                                   int C, int Kout, int R, int S, int OH,
                                   int OW, StepRole* l1, StepRole* l2) {
@@ -1411,13 +1351,6 @@ int conv_bwd_weight_combine_roles(float* ws, float* dw, int SK, int Nb,
                                     Kout, C, R * S, SK, l1, l2);
 }
 
-void launch_conv_small_bwdw_reduce(const float* partials, float* dw, int KO,
-                                   int C, int RS, int chunks, void* s) {
-  StepRole r = conv_small_bwdw_reduce_role(partials, dw, KO, C, RS, chunks);
-  conv_small_bwdw_reduce_k<<<r.gx, kBlock, 0, (hipStream_t)s>>>(
-      partials, dw, KO, C, RS, chunks);
-}
-
 // ws: conv_bwd_weight_ws_floats(Kout, Ncrs, SK) floats
 void launch_conv_bwd_weight(const float* dy, const float* x, float* dw,
                             float* ws, int SK, int Nb, int C, int H, int W,
@@ -1425,17 +1358,11 @@ void launch_conv_bwd_weight(const float* dy, const float* x, float* dw,
                             int stride, int pad, void* s) {
   launch_conv_bwd_weight_main(dy, x, ws, SK, Nb, C, H, W, Kout, R, S, OH, OW,
                               stride, pad, s);
-  int Ncrs = C * R * S;
-  if (conv_bwdw_small(Kout, Ncrs)) {
-    launch_conv_small_bwdw_reduce(ws, dw, Kout, C, R * S,
-                                  conv_small_bwdw_chunks((long)Nb * OH * OW),
-                                  s);
-    return;
-  }
-  // fused combine+permute (for SK==1 it degenerates to the permute of
-  // the directly-written rsc tensor)
-  launch_splitk_reduce_dwperm(conv_bwdw_target(ws, SK, Kout, Ncrs), dw, Kout,
-                              C, R * S, SK, s);
+  StepRole a, b;
+  int levels = conv_bwd_weight_combine_roles(ws, dw, SK, Nb, C, Kout, R, S,
+                                             OH, OW, &a, &b);
+  launch_step_role(&a, s);
+  if (levels == 2) launch_step_role(&b, s);
 }
 
 constexpr int kConvDbMaxChunks = 4096;
@@ -1449,7 +1376,7 @@ int conv_db_chunks(long M, int Kout) {
   return (int)c;
 }
 
-// Partials of launch_conv_db and launch_conv_db_bf16: one Kout row per
+// Partials of conv_db_roles and launch_conv_db_bf16: one Kout row per
 // chunk, sized for the most chunks conv_db_chunks can return.
 long conv_db_ws_floats(int Kout) { return (long)kConvDbMaxChunks * Kout; }
 
@@ -1458,7 +1385,9 @@ static int conv_db_kblk(int Kout) {
   return (kBlock % Kout == 0) ? Kout : kBlock;
 }
 
-// launch_conv_db as roles: *l1 the chunk partials, *l2 their fold
+// db[ko] = column sum of dy [M][Kout] (NHWC) in two levels: *l1 the chunk
+// partials, *l2 their fold.  The chunk count keeps >= 64k threads busy
+// whatever Kout is.
 void conv_db_roles(const float* dy, float* db, float* partials, int Nb,
                    int Kout, int OHW, StepRole* l1, StepRole* l2) {
   long M = (long)Nb * OHW;
@@ -1470,28 +1399,23 @@ void conv_db_roles(const float* dy, float* db, float* partials, int Nb,
   a.gx = (chunks + sub_per - 1) / sub_per;
   a.gy = (Kout + K_blk - 1) / K_blk;
   a.count = a.gx * a.gy;
-  a.p[0] = dy; a.p[1] = partials;
-  a.l0 = M;
-  a.i[0] = Kout; a.i[1] = chunks; a.i[2] = K_blk;
+  a.conv_db_stage1.dy = dy;
+  a.conv_db_stage1.partials = partials;
+  a.conv_db_stage1.M = M;
+  a.conv_db_stage1.Kout = Kout;
+  a.conv_db_stage1.chunks = chunks;
+  a.conv_db_stage1.K_blk = K_blk;
   *l1 = a;
   StepRole b{};
   b.kind = kRoleConvDbStage2;
   b.gx = Kout;
   b.gy = 1;
   b.count = Kout;
-  b.p[0] = partials; b.p[1] = db;
-  b.i[0] = Kout; b.i[1] = chunks;
+  b.conv_db_stage2.partials = partials;
+  b.conv_db_stage2.db = db;
+  b.conv_db_stage2.Kout = Kout;
+  b.conv_db_stage2.chunks = chunks;
   *l2 = b;
-}
-
-void launch_conv_db(const float* dy, float* db, float* partials, int Nb,
-                    int Kout, int OHW, void* s) {
-  hipStream_t st = (hipStream_t)s;
-  StepRole a, b;
-  conv_db_roles(dy, db, partials, Nb, Kout, OHW, &a, &b);
-  conv_db_stage1_k<<<dim3(a.gx, a.gy), kBlock, 0, st>>>(
-      dy, partials, a.l0, Kout, a.i[1], a.i[2]);
-  conv_db_stage2_k<<<b.gx, kBlock, 0, st>>>(partials, db, Kout, b.i[1]);
 }
 
 // The conv backward-weight split-K workspace, fp32 and bf16: SK slabs of
@@ -1501,36 +1425,8 @@ long conv_dwperm_ws_floats(int Kout, int Ncrs, int SK) {
   return (long)(SK + 1 + splitk_stage1_slabs(SK)) * Kout * Ncrs;
 }
 
-// ws: the first slab of a conv_dwperm_ws_floats workspace when SK > 1,
-// its rsc temp when SK == 1
-void launch_splitk_reduce_dwperm(const float* ws, float* dw, int Kout,
-                                 int C, int RS, int SK, void* s) {
-  // predicate, grids and the stage-1 offset live in
-  // splitk_reduce_dwperm_roles, shared with the queued path
-  StepRole a, b;
-  if (splitk_reduce_dwperm_roles(ws, dw, Kout, C, RS, SK, &a, &b) == 2) {
-    launch_splitk_partial((const float*)a.p[0], (float*)a.p[1], a.l0, a.i[0],
-                          a.i[1], s);
-    a = b;
-  }
-  splitk_reduce_dwperm_k<<<a.gx, kBlock, 0, (hipStream_t)s>>>(
-      (const float*)a.p[0], dw, Kout, C, RS, a.i[3]);
-}
-
-void launch_dwperm_rsc_crs(const float* in, float* out, int Kout, int C,
-                           int RS, void* s) {
-  dwperm_rsc_crs_k<<<grid_for((long)Kout * C * RS), kBlock, 0,
-                     (hipStream_t)s>>>(in, out, Kout, C, RS);
-}
-
-void launch_conv_db_stage2(const float* partials, float* db, int Kout,
-                           int chunks, void* s) {
-  conv_db_stage2_k<<<Kout, kBlock, 0, (hipStream_t)s>>>(partials, db, Kout,
-                                                        chunks);
-}
-
-// the two weight permutes as roles (kind: 0 = launch_wperm_crs_ko, the
-// forward's wt; 1 = launch_wperm_kors_c, bwd-data's wp)
+// the two weight permutes of w (Kout,C,R,S).  kind 0: the forward's wt,
+// out[((rs)*C + c)*Kout + ko]; 1: bwd-data's wp, out[((rs)*Kout + ko)*C + c]
 StepRole wperm_role(int kind, const float* w, float* out, int Kout, int C,
                     int RS) {
   StepRole r{};
@@ -1538,19 +1434,11 @@ StepRole wperm_role(int kind, const float* w, float* out, int Kout, int C,
   r.gx = grid_for((long)Kout * C * RS);
   r.gy = 1;
   r.count = r.gx;
-  r.p[0] = w; r.p[1] = out;
-  r.i[0] = Kout; r.i[1] = C; r.i[2] = RS;
+  r.wperm.w = w;
+  r.wperm.out = out;
+  r.wperm.Kout = Kout;
+  r.wperm.C = C;
+  r.wperm.RS = RS;
   return r;
-}
-
-void launch_wperm_crs_ko(const float* w, float* out, int Kout, int C, int RS,
-                         void* s) {
-  wperm_rsc_ko_k<<<wperm_role(0, w, out, Kout, C, RS).gx, kBlock, 0,
-                   (hipStream_t)s>>>(w, out, Kout, C, RS);
-}
-void launch_wperm_kors_c(const float* w, float* out, int Kout, int C, int RS,
-                         void* s) {
-  wperm_rsko_c_k<<<wperm_role(1, w, out, Kout, C, RS).gx, kBlock, 0,
-                   (hipStream_t)s>>>(w, out, Kout, C, RS);
 }
 }

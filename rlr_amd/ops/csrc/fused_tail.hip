@@ -6,16 +6,17 @@
 //                                       + dropout_fwd_dev_k
 //   dropout_unflatten_pool_bwd_relu_k = dropout_bwd_k + batch_transpose_k
 //                                       + maxpool2x2_bwd_gather4_k
-//   fc_head_rows_k + fc_head_reduce_k = dropout fwd, last-fc fwd, CE fwd,
+//   fc_head_rows_k + fc_head_reduce   = dropout fwd, last-fc fwd, CE fwd,
 //                                       loss mean, CE bwd, last-fc dx / dW /
 //                                       db, dropout+relu bwd (9 launches)
+//
+// (fc_head_reduce is a role: its body is in step_roles.h.)
 //
 // Every output is computed by the tail_math.h function the unfused kernel
 // calls, on the same operands in the same order; what a kernel boundary
 // rounded to a float is still one float here.  No atomics, no grid sync.
 #include "common.h"
 #include "launchers.h"
-#include "step_roles.h"
 #include "tail_math.h"
 
 // ============================================================ the seam
@@ -295,22 +296,10 @@ void fc_head_rows_k(const float* __restrict__ h1,
   }
 }
 
-// Stage B: the three reductions over the batch, one launch; a block takes
-// its role from its index.  dW: GEMM (M=C, N=H, K=B) with A = dlogits
-// consumed transposed; db: column sums of dlogits; loss: mean of the rows.
-__global__ __launch_bounds__(kBlock)
-void fc_head_reduce_k(const float* __restrict__ gl,
-                      const float* __restrict__ d2,
-                      const float* __restrict__ row_loss,
-                      float* __restrict__ dw, float* __restrict__ db,
-                      float* __restrict__ loss, int B, int H, int C,
-                      int dw_blocks, int db_blocks, int dw_wave) {
-  __shared__ float sh[kBlock];
-  fc_head_reduce_body(blockIdx.x, gl, d2, row_loss, dw, db, loss, B, H, C,
-                      dw_blocks, db_blocks, dw_wave, sh);
-}
+// Stage B, the three reductions over the batch, is a role: body in
+// step_roles.h, maker below (fc_head_reduce_role).
 
-// launch_gemm_f32's tiny-problem branch and its thread / wave choice
+// launch_gemm_f32_main's tiny-problem branch and its thread / wave choice
 static bool gemm_tiny(long M, long N, long K) {
   return M * N * K <= 8'000'000 && M * N <= 65536;
 }
@@ -389,24 +378,18 @@ StepRole fc_head_reduce_role(const float* ws, float* dw, float* db,
   r.gx = dw_blocks + db_blocks + 1;
   r.gy = 1;
   r.count = r.gx;
-  r.p[0] = gl; r.p[1] = d2; r.p[2] = row_loss;
-  r.p[3] = dw; r.p[4] = db; r.p[5] = loss;
-  r.i[0] = B; r.i[1] = H; r.i[2] = C;
-  r.i[3] = dw_blocks; r.i[4] = db_blocks; r.i[5] = dw_wave;
+  r.fc_head_reduce.gl = gl;
+  r.fc_head_reduce.d2 = d2;
+  r.fc_head_reduce.row_loss = row_loss;
+  r.fc_head_reduce.dw = dw;
+  r.fc_head_reduce.db = db;
+  r.fc_head_reduce.loss = loss;
+  r.fc_head_reduce.B = B;
+  r.fc_head_reduce.H = H;
+  r.fc_head_reduce.C = C;
+  r.fc_head_reduce.dw_blocks = dw_blocks;
+  r.fc_head_reduce.db_blocks = db_blocks;
+  r.fc_head_reduce.dw_wave = dw_wave;
   return r;
-}
-
-void launch_fc_head_step(const float* h1, const float* w, const float* bias,
-                         const long* labels, const float* dloss, float* ws,
-                         float* g_h1, float* dw, float* db, float* loss,
-                         int B, int H, int C, float p,
-                         const unsigned long long* state, int site,
-                         void* s) {
-  launch_fc_head_rows(h1, w, bias, labels, dloss, ws, g_h1, B, H, C, p, state,
-                      site, s);
-  StepRole r = fc_head_reduce_role(ws, dw, db, loss, B, H, C);
-  fc_head_reduce_k<<<r.gx, kBlock, 0, (hipStream_t)s>>>(
-      (const float*)r.p[0], (const float*)r.p[1], (const float*)r.p[2], dw,
-      db, loss, B, H, C, r.i[3], r.i[4], r.i[5]);
 }
 }

@@ -18,7 +18,6 @@
 // combines them.  No atomics anywhere: bitwise run-to-run reproducible.
 #include "common.h"
 #include "launchers.h"
-#include "step_roles.h"
 #include "tail_math.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -270,14 +269,8 @@ __global__ void splitk_reduce_wave_k(const float* __restrict__ ws,
   }
 }
 
-// (body: step_roles.h, shared with the role-batched launch)
-__global__ void splitk_reduce_k(const float* __restrict__ ws,
-                                float* __restrict__ C,
-                                const float* __restrict__ bias, int M, int N,
-                                int ldc, int SK, int relu) {
-  splitk_reduce_body(blockIdx.x, gridDim.x, ws, C, bias, M, N, ldc, SK, relu);
-}
-
+// (the thread-per-output form and the stage-1 fold of a deep split are
+// roles: bodies in step_roles.h, makers below)
 
 // Direct small GEMM: for tiny outputs (the 10/128-wide fc2 shapes) the
 // MFMA tile machinery + split-K reduce is pure overhead — a grid-stride
@@ -336,15 +329,6 @@ __global__ void gemm_small_wave_k(const float* __restrict__ A,
   }
 }
 
-// column sum: db[n] = sum_m dY[m][n] (bias gradient).
-// One wave per column; lane l accumulates rows l, l+64, ... then a shuffle
-// tree (deterministic).  Consecutive waves in a block handle consecutive
-// columns, so each lane-step reads a coalesced-ish (64*N-strided) front.
-__global__ void colsum_k(const float* __restrict__ dY,
-                         float* __restrict__ db, int M, int N) {
-  colsum_body(blockIdx.x, dY, db, M, N);
-}
-
 extern "C" {
 
 // Heuristic split-K: fill the chip (256 CUs) when the tile grid is
@@ -366,8 +350,8 @@ int gemm_f32_splitk(int M, int N, int K) {
   return (int)(sk < 1 ? 1 : (sk > 192 ? 192 : sk));
 }
 
-// Split-K workspace of launch_gemm_f32 and launch_gemm_bf16 (both combine
-// through launch_splitk_reduce): SK slabs of M*N partials, then the
+// Split-K workspace of launch_gemm_f32_main and launch_gemm_bf16 (both
+// combine through splitk_reduce_roles): SK slabs of M*N partials, then the
 // stage-1 slabs of a deep split.  No workspace for SK == 1.
 long gemm_splitk_ws_floats(int M, int N, int SK) {
   if (SK == 1) return 0;
@@ -431,24 +415,9 @@ int launch_gemm_f32_main(const float* A, const float* B, float* C,
   return SK > 1;
 }
 
-void launch_gemm_f32(const float* A, const float* B, float* C,
-                     const float* bias, float* ws, int M, int N, int K,
-                     int lda, int ldb, int ldc, int SK, int relu,
-                     int layout, void* s) {
-  if (launch_gemm_f32_main(A, B, C, bias, ws, M, N, K, lda, ldb, ldc, SK,
-                           relu, layout, s))
-    launch_splitk_reduce(ws, C, bias, M, N, ldc, SK, relu, s);
-}
-
 // stage-1 partial for deep split-K: each (output, 16-slab chunk) gets its
 // own thread — the single-stage thread-per-output form is parallelism-
 // starved when n_out is small and SK deep (e.g. 64 slabs x 32k outputs)
-__global__ void splitk_partial_k(const float* __restrict__ ws,
-                                 float* __restrict__ out, long n_out,
-                                 int S, int zstride) {
-  splitk_partial_body(blockIdx.x, gridDim.x, ws, out, n_out, S, zstride);
-}
-
 StepRole splitk_partial_role(const float* ws, float* out, long n_out, int S,
                              int zstride) {
   int chunks = (S + zstride - 1) / zstride;
@@ -457,9 +426,11 @@ StepRole splitk_partial_role(const float* ws, float* out, long n_out, int S,
   r.gx = grid_for(n_out * chunks);
   r.gy = 1;
   r.count = r.gx;
-  r.p[0] = ws; r.p[1] = out;
-  r.l0 = n_out;
-  r.i[0] = S; r.i[1] = zstride;
+  r.splitk_partial.ws = ws;
+  r.splitk_partial.out = out;
+  r.splitk_partial.n_out = n_out;
+  r.splitk_partial.S = S;
+  r.splitk_partial.zstride = zstride;
   return r;
 }
 
@@ -471,14 +442,22 @@ static StepRole splitk_reduce_role(const float* ws, float* C,
   r.gx = grid_for((long)M * N);
   r.gy = 1;
   r.count = r.gx;
-  r.p[0] = ws; r.p[1] = C; r.p[2] = bias;
-  r.i[0] = M; r.i[1] = N; r.i[2] = ldc; r.i[3] = SK; r.i[4] = relu;
+  r.splitk_reduce.ws = ws;
+  r.splitk_reduce.C = C;
+  r.splitk_reduce.bias = bias;
+  r.splitk_reduce.M = M;
+  r.splitk_reduce.N = N;
+  r.splitk_reduce.ldc = ldc;
+  r.splitk_reduce.SK = SK;
+  r.splitk_reduce.relu = relu;
   return r;
 }
 
-// launch_splitk_reduce as roles, by the same predicates: returns the
-// number of levels, 2 (*l1 folds, *l2 finishes), 1 (*l1 is the thread-form
-// reduce) or 0: the wave form has no role, the caller launches it.
+// The split-K combine as roles: returns the number of levels, 2 (*l1
+// folds, *l2 finishes), 1 (*l1 is the thread-form reduce) or 0: the wave
+// form has no role, launch_splitk_reduce runs it.  ws holds
+// gemm_splitk_ws_floats(M, N, SK) floats: the stage-1 scratch is the
+// splitk_stage1_slabs(SK) slabs after the SK partials.
 int splitk_reduce_roles(const float* ws, float* C, const float* bias, int M,
                         int N, int ldc, int SK, int relu, StepRole* l1,
                         StepRole* l2) {
@@ -495,6 +474,7 @@ int splitk_reduce_roles(const float* ws, float* C, const float* bias, int M,
   return 1;
 }
 
+// column sum: db[n] = sum_m dY[m][n] (bias gradient), one wave per column
 StepRole colsum_role(const float* dY, float* db, int M, int N) {
   int wpb = kBlock / kWave;
   StepRole r{};
@@ -502,47 +482,27 @@ StepRole colsum_role(const float* dY, float* db, int M, int N) {
   r.gx = (N + wpb - 1) / wpb;
   r.gy = 1;
   r.count = r.gx;
-  r.p[0] = dY; r.p[1] = db;
-  r.i[0] = M; r.i[1] = N;
+  r.colsum.dY = dY;
+  r.colsum.db = db;
+  r.colsum.M = M;
+  r.colsum.N = N;
   return r;
 }
 
-// ws holds gemm_splitk_ws_floats(M, N, SK) floats: the stage-1 scratch is
-// the splitk_stage1_slabs(SK) slabs after the SK partials
+// the combine now: its roles in order, or the wave form
 void launch_splitk_reduce(const float* ws, float* C, const float* bias,
                           int M, int N, int ldc, int SK, int relu, void* s) {
-  // the predicates, grids and ws offsets live in splitk_reduce_roles: the
-  // queued path and this one cannot drift apart
-  hipStream_t st = (hipStream_t)s;
   StepRole a, b;
   int levels = splitk_reduce_roles(ws, C, bias, M, N, ldc, SK, relu, &a, &b);
   if (levels == 0) {
     long n_out = (long)M * N;
     int wpb = kBlock / kWave;
-    splitk_reduce_wave_k<<<(n_out + wpb - 1) / wpb, kBlock, 0, st>>>(
-        ws, C, bias, M, N, ldc, SK, relu);
+    splitk_reduce_wave_k<<<(n_out + wpb - 1) / wpb, kBlock, 0,
+                           (hipStream_t)s>>>(ws, C, bias, M, N, ldc, SK,
+                                             relu);
     return;
   }
-  if (levels == 2) {
-    splitk_partial_k<<<a.gx, kBlock, 0, st>>>(
-        (const float*)a.p[0], (float*)a.p[1], a.l0, a.i[0], a.i[1]);
-    a = b;
-  }
-  splitk_reduce_k<<<a.gx, kBlock, 0, st>>>(
-      (const float*)a.p[0], (float*)a.p[1], (const float*)a.p[2], a.i[0],
-      a.i[1], a.i[2], a.i[3], a.i[4]);
-}
-
-
-void launch_splitk_partial(const float* ws, float* out, long n_out,
-                           int S, int zstride, void* s) {
-  StepRole r = splitk_partial_role(ws, out, n_out, S, zstride);
-  splitk_partial_k<<<r.gx, kBlock, 0, (hipStream_t)s>>>(ws, out, n_out, S,
-                                                        zstride);
-}
-
-void launch_colsum(const float* dY, float* db, int M, int N, void* s) {
-  StepRole r = colsum_role(dY, db, M, N);
-  colsum_k<<<r.gx, kBlock, 0, (hipStream_t)s>>>(dY, db, M, N);
+  launch_step_role(&a, s);
+  if (levels == 2) launch_step_role(&b, s);
 }
 }

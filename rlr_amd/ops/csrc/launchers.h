@@ -8,12 +8,39 @@
 #pragma once
 #include <cstdint>
 
-// One entry of a role-batched launch (step_batch.hip): `count` consecutive
-// blocks starting at flat block `first` run the body `kind` as the blocks
-// of a virtual (gx, gy) grid, count == gx * gy.  p / l0 / i are the body's
-// pointers and integers in the order of its stand-alone kernel's arguments.
-// Each role maker below fills everything but `first`, which the launch
-// assigns (step_batch_plan).
+// A role: one small fold / permute / copy kernel of a training step, as
+// data.  `kind` names its body (step_roles.h); the union member of that name
+// holds the body's arguments, named and typed as the body reads them.  The
+// body runs as the blocks of a (gx, gy) grid, count == gx * gy: alone
+// (launch_step_role), or as blocks [first, first + count) of a batched
+// launch, which assigns `first`.  The role makers below fill the rest.
+struct ConvDbStage1Args {
+  const float* dy; float* partials; long M; int Kout, chunks, K_blk;
+};
+struct ConvDbStage2Args { const float* partials; float* db; int Kout, chunks; };
+struct SplitkPartialArgs {
+  const float* ws; float* out; long n_out; int S, zstride;
+};
+struct SplitkReduceArgs {
+  const float* ws; float* C; const float* bias; int M, N, ldc, SK, relu;
+};
+struct SplitkReduceDwpermArgs {
+  const float* ws; float* dw; int Kout, C, RS, SK;
+};
+struct ConvSmallBwdwReduceArgs {
+  const float* partials; float* dw; int KO, C, RS, chunks;
+};
+struct ColsumArgs { const float* dY; float* db; int M, N; };
+struct FcHeadReduceArgs {
+  const float *gl, *d2, *row_loss; float *dw, *db, *loss;
+  int B, H, C, dw_blocks, db_blocks, dw_wave;
+};
+struct WpermArgs { const float* w; float* out; int Kout, C, RS; };
+struct GatherRowsArgs {
+  const uint32_t* src; const long* sel; uint32_t* dst; long rows;
+  int row_words, vec, src_rows;
+};
+struct AddU64Args { unsigned long long* p; unsigned long long delta; };
 enum StepRoleKind {
   kRoleConvDbStage1 = 0,
   kRoleConvDbStage2,
@@ -27,24 +54,36 @@ enum StepRoleKind {
   kRoleWpermRskoC,
   kRoleGatherRows,
   kRoleAddU64,
+  kStepRoleKinds,
 };
 struct StepRole {
   int kind;
   int first;
   int count;
   int gx, gy;
-  int i[6];
-  long l0;
-  const void* p[6];
+  union {
+    ConvDbStage1Args conv_db_stage1;
+    ConvDbStage2Args conv_db_stage2;
+    SplitkPartialArgs splitk_partial;
+    SplitkReduceArgs splitk_reduce;
+    SplitkReduceDwpermArgs splitk_reduce_dwperm;
+    ConvSmallBwdwReduceArgs conv_small_bwdw_reduce;
+    ColsumArgs colsum;
+    FcHeadReduceArgs fc_head_reduce;
+    WpermArgs wperm;  // both wperm kinds
+    GatherRowsArgs gather_rows;
+    AddU64Args add_u64;
+  };
 };
+static_assert(sizeof(StepRole) <= 104, "16 of them are kernel arguments");
 constexpr int kStepMaxRoles = 16;
 
 extern "C" {
-// step_batch.hip.  step_batch_plan: first[r] = blocks of the roles before
-// r, returns the total (host arithmetic only).  launch_step_batch runs up
-// to kStepMaxRoles roles in one launch (more: returns -1 and launches
-// nothing; 0 otherwise); roles with count == 0 are skipped, and nothing is
-// launched when every count is 0.
+// step_batch.hip.  launch_step_role runs one role now, launch_step_batch up
+// to kStepMaxRoles in one launch; both skip roles with count == 0 and return
+// 0, or -1 (nothing launched) for an unknown kind or too many roles.
+// step_batch_plan (host only): first[r] = blocks before r; returns the total.
+int launch_step_role(const StepRole* r, void* s);
 int step_batch_max_roles();
 int step_batch_plan(const int* counts, int n, int* first);
 int step_batch_lookup(const int* counts, int n, int block, int* vblock);
@@ -152,19 +191,12 @@ void launch_dropout_unflatten_pool_bwd_relu(const float* g,
                                             long B, int H, int W, int C,
                                             float p, void* s);
 // The classifier head on h1 (B,H), w (C,H), bias (C): dropout, fc, CE
-// forward and backward in two launches.  fc_head_fused_ok(B, H, C): C <= 64
-// and the three fc GEMMs all take launch_gemm_f32's tiny-problem branch.
-// ws: fc_head_ws_floats(B, H, C) floats.
+// forward and backward: stage A (per row) launched, stage B (over the batch)
+// a role over the ws (fc_head_ws_floats(B, H, C) floats) that A filled.
+// fc_head_fused_ok(B, H, C): C <= 64 and the three fc GEMMs all take
+// launch_gemm_f32_main's tiny-problem branch.
 int fc_head_fused_ok(int B, int H, int C);
 long fc_head_ws_floats(int B, int H, int C);
-void launch_fc_head_step(const float* h1, const float* w, const float* bias,
-                         const long* labels, const float* dloss, float* ws,
-                         float* g_h1, float* dw, float* db, float* loss,
-                         int B, int H, int C, float p,
-                         const unsigned long long* state, int site,
-                         void* s);
-// launch_fc_head_step's two stages apart: stage A launched, stage B as a
-// role of a batched launch over the same ws
 void launch_fc_head_rows(const float* h1, const float* w, const float* bias,
                          const long* labels, const float* dloss, float* ws,
                          float* g_h1, int B, int H, int C, float p,
@@ -222,22 +254,19 @@ void launch_pairwise_sqdist(const double* U, int K, long n, double* ws,
 // gemm_f32.hip
 int gemm_f32_splitk(int M, int N, int K);
 long gemm_splitk_ws_floats(int M, int N, int SK);
-void launch_gemm_f32(const float* A, const float* B, float* C,
-                     const float* bias, float* ws, int M, int N, int K,
-                     int lda, int ldb, int ldc, int SK, int relu,
-                     int layout, void* s);
-void launch_colsum(const float* dY, float* db, int M, int N, void* s);
-// launch_gemm_f32 without its split-K combine: returns 1 when ws holds SK
-// partial slabs that still have to be folded into C
+// the GEMM without its split-K combine: returns 1 when ws holds SK partial
+// slabs that still have to be folded into C, 0 when C is complete
 int launch_gemm_f32_main(const float* A, const float* B, float* C,
                          const float* bias, float* ws, int M, int N, int K,
                          int lda, int ldb, int ldc, int SK, int relu,
                          int layout, void* s);
-// launch_splitk_reduce as roles: the number of levels filled, 0 when the
-// launcher would take its wave form (no role: launch it instead)
+// the split-K combine as roles: the number of levels filled, 0 for the wave
+// form, which has no role.  launch_splitk_reduce: the combine now, any form.
 int splitk_reduce_roles(const float* ws, float* C, const float* bias, int M,
                         int N, int ldc, int SK, int relu, StepRole* l1,
                         StepRole* l2);
+void launch_splitk_reduce(const float* ws, float* C, const float* bias,
+                          int M, int N, int ldc, int SK, int relu, void* s);
 StepRole splitk_partial_role(const float* ws, float* out, long n_out, int S,
                              int zstride);
 StepRole colsum_role(const float* dY, float* db, int M, int N);
@@ -256,18 +285,15 @@ void launch_conv_bwd_data_relu(const float* dy, const float* wp,
                                int C, int H, int W, int Kout, int R, int S,
                                int OH, int OW, int stride, int pad,
                                void* s);
-void launch_conv_bwd_data(const float* dy, const float* wp, float* dx,
-                          int Nb, int C, int H, int W, int Kout, int R,
-                          int S, int OH, int OW, int stride, int pad,
-                          void* s);
 int conv_bwd_weight_splitk(int Kout, int Ncrs, long Kdim);
 long conv_bwd_weight_ws_floats(int Kout, int Ncrs, int SK);
+// launch_conv_bwd_weight = main kernels + the combine roles (1 or 2 levels)
+// over ws; a small layer's ws: conv_small_bwdw_chunks(Nb*OH*OW) chunk slabs
+int conv_small_bwdw_chunks(long Kdim);
 void launch_conv_bwd_weight(const float* dy, const float* x, float* dw,
                             float* ws, int SK, int Nb, int C, int H, int W,
                             int Kout, int R, int S, int OH, int OW,
                             int stride, int pad, void* s);
-// launch_conv_bwd_weight as main kernels + combine: the combine either
-// launched, or as roles (1 or 2 levels) over the ws the main kernels filled
 void launch_conv_bwd_weight_main(const float* dy, const float* x, float* ws,
                                  int SK, int Nb, int C, int H, int W,
                                  int Kout, int R, int S, int OH, int OW,
@@ -277,21 +303,13 @@ int conv_bwd_weight_combine_roles(float* ws, float* dw, int SK, int Nb,
                                   int OW, StepRole* l1, StepRole* l2);
 int splitk_reduce_dwperm_roles(const float* ws, float* dw, int Kout, int C,
                                int RS, int SK, StepRole* l1, StepRole* l2);
-void launch_conv_small_bwdw_reduce(const float* partials, float* dw, int KO,
-                                   int C, int RS, int chunks, void* s);
 void conv_db_roles(const float* dy, float* db, float* partials, int Nb,
                    int Kout, int OHW, StepRole* l1, StepRole* l2);
 StepRole wperm_role(int kind, const float* w, float* out, int Kout, int C,
                     int RS);
 int conv_db_chunks(long M, int Kout);
 long conv_db_ws_floats(int Kout);
-void launch_conv_db(const float* dy, float* db, float* partials, int Nb,
-                    int Kout, int OHW, void* s);
 long conv_dwperm_ws_floats(int Kout, int Ncrs, int SK);
-void launch_wperm_crs_ko(const float* w, float* out, int Kout, int C, int RS,
-                         void* s);
-void launch_wperm_kors_c(const float* w, float* out, int Kout, int C, int RS,
-                         void* s);
 // conv_bf16.hip
 int conv_bwd_weight_bf16_splitk(int Kout, int Ncrs, long Kdim);
 void launch_conv_fwd_bf16(const unsigned short* x, const unsigned short* wt,
@@ -306,11 +324,6 @@ void launch_conv_bwd_data_bf16_relu(const unsigned short* dy,
                                     int C, int H, int W, int Kout, int R,
                                     int S, int OH, int OW, int stride,
                                     int pad, void* s);
-void launch_conv_bwd_data_bf16(const unsigned short* dy,
-                               const unsigned short* wp, unsigned short* dx,
-                               int Nb, int C, int H, int W, int Kout, int R,
-                               int S, int OH, int OW, int stride, int pad,
-                               void* s);
 void launch_conv_bwd_weight_bf16(const unsigned short* dy,
                                  const unsigned short* x, float* dw,
                                  float* ws, int SK, int Nb, int C, int H,
@@ -397,20 +410,6 @@ void launch_poison_subf(float* data, const long* idxs, int B,
 void launch_normalize_u8(const uint8_t* raw, float* out, long B, int H,
                          int W, int C, const float* mean, const float* stdv,
                          void* s);
-
-// ---- internal: helpers shared between sibling kernel files only ----
-// gemm_f32.hip
-void launch_splitk_reduce(const float* ws, float* C, const float* bias,
-                          int M, int N, int ldc, int SK, int relu, void* s);
-void launch_splitk_partial(const float* ws, float* out, long n_out, int S,
-                           int zstride, void* s);
-// conv_f32.hip
-void launch_splitk_reduce_dwperm(const float* ws, float* dw, int Kout,
-                                 int C, int RS, int SK, void* s);
-void launch_dwperm_rsc_crs(const float* in, float* out, int Kout, int C,
-                           int RS, void* s);
-void launch_conv_db_stage2(const float* partials, float* db, int Kout,
-                           int chunks, void* s);
 // conv_bf16.hip (the variant sweep of tests/perf/bwdw_micro.hip)
 void launch_conv_bwd_weight_bf16_ex(const unsigned short* dy,
                                     const unsigned short* x, float* dw,

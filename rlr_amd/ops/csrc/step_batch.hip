@@ -1,16 +1,20 @@
-// Role-batched launch (gfx950, fp32): up to kStepMaxRoles of a training
-// step's small fold / permute / copy kernels in ONE launch.  Each of them
+// The two kernels that run a step's roles (gfx950, fp32).  A role is one of
+// a training step's small fold / permute / copy kernels as data: a StepRole
+// (launchers.h) made by the maker beside the kernels it belongs to, run by
+// step_role_run (step_roles.h).  step_role_k<KIND> runs one role alone, now;
+// step_batch_k runs up to kStepMaxRoles of them in ONE launch.  Each of them
 // sits on the floor of a graph-replayed launch and none depends on a big
 // kernel after it, so the step queues them and issues them together (see
 // docs/KERNELS.md "Step batching").
 //
 // The table of roles travels by value in the kernel arguments.  A block
 // finds its role by scanning the block prefix; the choice is uniform over
-// the block, so a body may keep its barriers.  The bodies are the
-// stand-alone kernels' bodies (step_roles.h), called with the block index
-// inside the role and the role's own grid size: what a role writes is
-// bitwise what its stand-alone kernel writes.  No atomics, no grid sync;
-// roles of one launch must not depend on each other.
+// the block, so a body may keep its barriers.  Both kernels call the same
+// step_role_run with the block index inside the role's grid: what a role
+// writes in a batch is bitwise what it writes alone.  No atomics, no grid
+// sync; roles of one launch must not depend on each other.
+#include <utility>
+
 #include "common.h"
 #include "launchers.h"
 #include "step_roles.h"
@@ -27,62 +31,28 @@ void step_batch_k(const StepTable t) {
   if (ri < 0) return;
   const StepRole& r = t.r[ri];
   const int v = (int)blockIdx.x - r.first;
-  const int bx = v % r.gx, by = v / r.gx;
-  const int gx = r.gx;
-  switch (r.kind) {
-    case kRoleConvDbStage1:
-      conv_db_stage1_body(bx, by, (const float*)r.p[0], (float*)r.p[1], r.l0,
-                          r.i[0], r.i[1], r.i[2]);
-      break;
-    case kRoleConvDbStage2:
-      conv_db_stage2_body(bx, (const float*)r.p[0], (float*)r.p[1], r.i[0],
-                          r.i[1], sh);
-      break;
-    case kRoleSplitkPartial:
-      splitk_partial_body(bx, gx, (const float*)r.p[0], (float*)r.p[1], r.l0,
-                          r.i[0], r.i[1]);
-      break;
-    case kRoleSplitkReduce:
-      splitk_reduce_body(bx, gx, (const float*)r.p[0], (float*)r.p[1],
-                         (const float*)r.p[2], r.i[0], r.i[1], r.i[2],
-                         r.i[3], r.i[4]);
-      break;
-    case kRoleSplitkReduceDwperm:
-      splitk_reduce_dwperm_body(bx, gx, (const float*)r.p[0],
-                                (float*)r.p[1], r.i[0], r.i[1], r.i[2],
-                                r.i[3]);
-      break;
-    case kRoleConvSmallBwdwReduce:
-      conv_small_bwdw_reduce_body(bx, (const float*)r.p[0], (float*)r.p[1],
-                                  r.i[0], r.i[1], r.i[2], r.i[3]);
-      break;
-    case kRoleColsum:
-      colsum_body(bx, (const float*)r.p[0], (float*)r.p[1], r.i[0], r.i[1]);
-      break;
-    case kRoleFcHeadReduce:
-      fc_head_reduce_body(bx, (const float*)r.p[0], (const float*)r.p[1],
-                          (const float*)r.p[2], (float*)r.p[3],
-                          (float*)r.p[4], (float*)r.p[5], r.i[0], r.i[1],
-                          r.i[2], r.i[3], r.i[4], r.i[5], sh);
-      break;
-    case kRoleWpermRscKo:
-      wperm_rsc_ko_body(bx, gx, (const float*)r.p[0], (float*)r.p[1], r.i[0],
-                        r.i[1], r.i[2]);
-      break;
-    case kRoleWpermRskoC:
-      wperm_rsko_c_body(bx, gx, (const float*)r.p[0], (float*)r.p[1], r.i[0],
-                        r.i[1], r.i[2]);
-      break;
-    case kRoleGatherRows:
-      gather_rows_body(bx, gx, (const uint32_t*)r.p[0], (const long*)r.p[1],
-                       (uint32_t*)r.p[2], r.l0, r.i[0], r.i[1], r.i[2]);
-      break;
-    case kRoleAddU64:
-      add_u64_body((unsigned long long*)r.p[0], (unsigned long long)r.l0);
-      break;
-    default:
-      break;
+  step_role_run(r.kind, r, v % r.gx, v / r.gx, sh);
+}
+
+// one role on its own grid (gx, gy); LDS only for the kinds that use it
+template <int KIND>
+__global__ __launch_bounds__(kBlock)
+void step_role_k(const StepRole r) {
+  float* sh = nullptr;
+  if constexpr (step_role_uses_lds(KIND)) {
+    __shared__ float lds[kBlock];
+    sh = lds;
   }
+  step_role_run(KIND, r, (int)blockIdx.x, (int)blockIdx.y, sh);
+}
+
+// step_role_k<kind>, one instantiation per StepRoleKind
+using StepRoleKernel = void (*)(StepRole);
+template <int... KIND>
+static StepRoleKernel step_role_kernel(int kind,
+                                       std::integer_sequence<int, KIND...>) {
+  static const StepRoleKernel table[] = {step_role_k<KIND>...};
+  return table[kind];
 }
 
 extern "C" {
@@ -116,6 +86,16 @@ int step_batch_lookup(const int* counts, int n, int block, int* vblock) {
   return ri;
 }
 
+// returns 0, or -1 (nothing launched) for a kind that does not exist
+int launch_step_role(const StepRole* r, void* s) {
+  if (r->kind < 0 || r->kind >= kStepRoleKinds) return -1;
+  if (r->count <= 0) return 0;
+  StepRoleKernel k = step_role_kernel(
+      r->kind, std::make_integer_sequence<int, kStepRoleKinds>{});
+  k<<<dim3(r->gx, r->gy), kBlock, 0, (hipStream_t)s>>>(*r);
+  return 0;
+}
+
 // returns 0, or -1 (nothing launched) when n > kStepMaxRoles
 int launch_step_batch(const StepRole* roles, int n, void* s) {
   if (n <= 0) return 0;
@@ -137,7 +117,7 @@ int launch_step_batch(const StepRole* roles, int n, void* s) {
 }
 
 // dst row r = src row sel[r], rows of row_words 32-bit words; sel must
-// index [0, src_rows) (gather_rows_body never reads outside it)
+// index [0, src_rows) (the body never reads outside it)
 StepRole step_role_gather_rows(const void* src, const long* sel, void* dst,
                                long rows, int row_words, int src_rows) {
   int vec = (row_words % 4) == 0 && ((uintptr_t)src % 16) == 0 &&
@@ -148,9 +128,13 @@ StepRole step_role_gather_rows(const void* src, const long* sel, void* dst,
   r.gx = items > 0 ? grid_for(items) : 0;
   r.gy = 1;
   r.count = r.gx;
-  r.p[0] = src; r.p[1] = sel; r.p[2] = dst;
-  r.l0 = rows;
-  r.i[0] = row_words; r.i[1] = vec; r.i[2] = src_rows;
+  r.gather_rows.src = (const uint32_t*)src;
+  r.gather_rows.sel = sel;
+  r.gather_rows.dst = (uint32_t*)dst;
+  r.gather_rows.rows = rows;
+  r.gather_rows.row_words = row_words;
+  r.gather_rows.vec = vec;
+  r.gather_rows.src_rows = src_rows;
   return r;
 }
 
@@ -160,8 +144,8 @@ StepRole step_role_add_u64(unsigned long long* p, unsigned long long delta) {
   r.gx = 1;
   r.gy = 1;
   r.count = 1;
-  r.p[0] = p;
-  r.l0 = (long)delta;
+  r.add_u64.p = p;
+  r.add_u64.delta = delta;
   return r;
 }
 }

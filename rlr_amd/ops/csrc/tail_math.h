@@ -87,7 +87,7 @@ __device__ __forceinline__ float wave_tree_down(float acc) {
   return acc;
 }
 
-// colsum_k: lane-strided rows of column n, then the same tree
+// the colsum role: lane-strided rows of column n, then the same tree
 __device__ __forceinline__ float colsum_wave(const float* __restrict__ dY,
                                              int M, int N, int n, int lane) {
   float acc = 0.f;

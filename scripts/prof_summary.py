@@ -5,8 +5,24 @@ Usage: python scripts/prof_summary.py <results.db> [top_n]
 Prints total-ms / calls / avg-us per kernel, descending total.
 (rocprofv3 on this image emits SQLite .db instead of CSV stats.)"""
 
+import re
 import sqlite3
 import sys
+
+# step_role_k<KIND> (step_batch.hip) runs one role alone; KIND counts
+# through StepRoleKind (launchers.h) in this order
+ROLE_KINDS = ['conv_db_stage1', 'conv_db_stage2', 'splitk_partial',
+              'splitk_reduce', 'splitk_reduce_dwperm',
+              'conv_small_bwdw_reduce', 'colsum', 'fc_head_reduce',
+              'wperm_rsc_ko', 'wperm_rsko_c', 'gather_rows', 'add_u64']
+
+
+def readable(name):
+    """step_role_k<3>(StepRole) -> step_role_k<splitk_reduce>"""
+    m = re.search(r'step_role_k<(\d+)>', name)
+    if not m or int(m.group(1)) >= len(ROLE_KINDS):
+        return name
+    return f'step_role_k<{ROLE_KINDS[int(m.group(1))]}>'
 
 
 def summarize(path, top=30):
@@ -27,7 +43,7 @@ def summarize(path, top=30):
     print("|---|---|---|---|---|")
     for name, n, avg, tot in rows:
         print(f"| {tot:.1f} | {n} | {avg:.1f} | {100*tot/total:.1f} "
-              f"| `{name[:70]}` |")
+              f"| `{readable(name)[:70]}` |")
     print(f"\n(sum of listed: {total:.1f} ms)")
 
 

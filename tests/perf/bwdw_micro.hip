@@ -6,8 +6,10 @@
 // element -> bitwise-equal fp32 results).
 //
 // Build (linked against the extension objects):
-//   hipcc --offload-arch=gfx950 -O3 tests/perf/bwdw_micro.hip \
-//     rlr_amd/ops/csrc/build/{conv_bf16.o,conv_f32.o,gemm_f32.o} \
+//   hipcc --offload-arch=gfx950 -O3 -c tests/perf/bwdw_micro.hip \
+//     -o tests/perf/bwdw_micro.o
+//   hipcc --offload-arch=gfx950 tests/perf/bwdw_micro.o \
+//     rlr_amd/ops/csrc/build/{conv_bf16,conv_f32,gemm_f32,step_batch}.o \
 //     -o tests/perf/bwdw_micro
 #include <hip/hip_runtime.h>
 #include <cstdio>

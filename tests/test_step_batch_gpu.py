@@ -83,6 +83,29 @@ def test_plan_zero_block_roles(E):
     _check_plan(E, [0] * (n - 1) + [3])
 
 
+def test_prof_summary_names_every_role_kind():
+    """scripts/prof_summary.py prints step_role_k<KIND> by the kind's name:
+    its list follows StepRoleKind (launchers.h), entry for entry."""
+    import importlib.util
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, 'rlr_amd', 'ops', 'csrc',
+                           'launchers.h')) as f:
+        body = re.search(r'enum StepRoleKind \{(.*?)\};', f.read(),
+                         re.S).group(1)
+    kinds = re.findall(r'kRole(\w+)', body)
+    snake = [re.sub(r'(?<!^)(?=[A-Z])', '_', k).lower() for k in kinds]
+    spec = importlib.util.spec_from_file_location(
+        'prof_summary', os.path.join(root, 'scripts', 'prof_summary.py'))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    assert len(snake) == 12 and mod.ROLE_KINDS == snake
+    assert (mod.readable('void step_role_k<6>(StepRole)')
+            == 'step_role_k<colsum>')
+    assert mod.readable('step_batch_k(StepTable)') == 'step_batch_k(StepTable)'
+
+
 # ----------------------------------------------------------------- 2. roles
 
 def filled_queue(E):
@@ -255,7 +278,7 @@ def test_role_gather(E):
                                    (5, 24, 10)])    # thread-form dW
 def test_role_fc_head_reduce(E, B, H, C):
     """fc_head_step with the queue (stage B as a role behind two others)
-    against fc_head_step without it (fc_head_reduce_k launched)."""
+    against fc_head_step without it (the same role, run alone)."""
     assert E.fc_head_fused_ok(B, H, C)
     h1 = rnd(B, H, seed=B).relu()
     w, b = rnd(C, H, seed=1), rnd(C, seed=2)
