@@ -8,8 +8,9 @@ attacks, with FedAvg / coordinate-median / sign aggregation modulated by the
 per-parameter robust-learning-rate sign vote.  Build addition: the
 coordinate-wise trimmed mean (--aggr trmean, Yin et al. 2018), sharing one
 LDS sorting-network kernel family with the median at more than 64 sampled
-agents, and Krum / Multi-Krum (--aggr krum, Blanchard et al. 2017) on an
-fp64 MFMA pairwise-distance kernel.
+agents, Krum / Multi-Krum (--aggr krum, Blanchard et al. 2017) on an
+fp64 MFMA pairwise-distance kernel, and the geometric median / RFA
+(--aggr geomed, Pillutla et al.) on a fused Weiszfeld distance kernel.
 
 Architecture (nothing here is a port):
   * one process per GPU; sampled agents are sharded contiguously across

@@ -42,6 +42,26 @@ Rules (each a HIP kernel on the GPU path, ops/csrc/aggregation.hip):
     vote decides the direction.  Noise behaves as for avg on each backend.
     BatchNorm buffers are averaged unweighted over the same selection.
     Non-finite updates are out of scope (0 * inf is NaN).
+  * geometric median / RFA (build addition, --aggr geomed; Pillutla et
+    al., "Robust Aggregation for Federated Learning"): smoothed Weiszfeld,
+    UNWEIGHTED like comed/trmean/krum, started at the plain mean.  With
+    R = --geomed_iters and nu = --geomed_nu:
+        a = ones(K)
+        repeat R times:
+            s     = a[0] + a[1] + ... + a[K-1]        sequential
+            z_j   = (sum_k a[k] U[k][j]) * (1 / s)    sequential in k from 0
+            d2[k] = sum_j (U[k][j] - z_j)^2           fp64
+            a[k]  = 1 / max(nu, sqrt(d2[k]))
+        aggregate = (sum_k a[k] U[k]) * (1 / sum a)
+    i.e. the weighted-avg path with w = a; R = 0 is the unweighted mean.
+    On the GPU the distances come from ops/csrc/geomed.hip (one streaming
+    pass over U per iteration, no host sync inside the loop) and the last
+    line is the fused avg kernel.  A smooth re-weighting, not a selection:
+    the RLR vote is over ALL K, noise behaves as for avg on each backend,
+    BatchNorm buffers are averaged with the same final weights.  The two
+    backends agree to rounding, not bit for bit (the sum over n is chunked
+    on the GPU); each is a pure function of its input.  last_weights holds
+    the final a normalised to sum 1.
   * sign (aggregation.py:71-75): sign(sum_k sign(U_k)).
   * optional N(0, noise*clip) gaussian noise (aggregation.py:34-35) from a
     per-round derived stream.  NOTE: the fused GPU avg path draws noise
@@ -75,6 +95,7 @@ class Aggregation:
         self.poisoned_val_loader = poisoned_val_loader
         self.cum_net_mov = 0.0
         self.last_selected = None   # krum: sampled positions kept last round
+        self.last_weights = None    # geomed: final weights, normalised
 
     # ------------------------------------------------------------- entry
 
@@ -94,12 +115,20 @@ class Aggregation:
             self.last_selected = self.krum_select(stacked)
             self._log_krum(agent_ids, cur_round)
 
-        if _gpu(stacked) and (self.args.aggr == 'avg' or krum):
+        geomed = self.args.aggr == 'geomed'
+        if geomed:
+            a = self.geomed_weights(stacked)
+            self.last_weights = a / a.sum()
+            self._log_geomed(agent_ids, cur_round)
+
+        if _gpu(stacked) and (self.args.aggr == 'avg' or krum or geomed):
             # headline path: ONE fused kernel does sign-vote + weighted avg
             # + noise + fp32 apply in a single pass over the K x n matrix
-            # (krum: 0/1 weights over the selection, vote over all K)
+            # (krum: 0/1 weights over the selection, geomed: the Weiszfeld
+            # weights; vote over all K)
             from .utils.rng import derive_seed
             w = (self._krum_weights(stacked.shape[0], stacked.device) if krum
+                 else a if geomed
                  else self._weights(agent_ids, stacked.device))
             noise_std = (self.args.noise * self.args.clip
                          if self.args.noise > 0 else 0.0)
@@ -143,6 +172,8 @@ class Aggregation:
             agg = self.agg_sign(stacked)
         elif krum:
             agg = self._krum_mean(stacked, self.last_selected)
+        elif geomed:
+            agg = self._geomed_mean(stacked, a)
         else:
             raise ValueError(self.args.aggr)
 
@@ -309,6 +340,60 @@ class Aggregation:
                         if agent_ids[p] < self.args.num_corrupt)
             self.writer.add_scalar('Krum/Corrupt_Selected', n_bad, cur_round)
 
+    # ------------------------------------------------------------ geomed
+
+    def _geomed_loop(self, stacked):
+        """The rule as written in the module docstring, in plain torch."""
+        K = stacked.shape[0]
+        nu = float(self.args.geomed_nu)
+        a = torch.ones(K, dtype=torch.float64, device=stacked.device)
+        for _ in range(int(self.args.geomed_iters)):
+            d2 = ((stacked - self._geomed_mean(stacked, a)) ** 2).sum(1)
+            a = 1.0 / torch.sqrt(d2).clamp(min=nu)
+        return a
+
+    def geomed_weights(self, stacked):
+        """Raw Weiszfeld weights a[k] = 1 / max(nu, ||U_k - z||) after
+        geomed_iters updates from a = ones (ones for geomed_iters = 0)."""
+        if self.args.geomed_iters < 0 or not self.args.geomed_nu > 0:
+            raise ValueError(
+                f"geomed_iters={self.args.geomed_iters} must be >= 0 and "
+                f"geomed_nu={self.args.geomed_nu} must be > 0")
+        if _gpu(stacked) and stacked.shape[0] <= ext().geomed_max_k():
+            return ext().geomed_weights(stacked, int(self.args.geomed_iters),
+                                        float(self.args.geomed_nu))[0]
+        # the CPU reference; above the kernel's K limit the same loop on
+        # the device
+        return self._geomed_loop(stacked)
+
+    @staticmethod
+    def _geomed_mean(stacked, a):
+        """(sum_k a[k] U[k]) * (1 / sum a), both sums sequential from 0."""
+        s = torch.zeros((), dtype=torch.float64, device=stacked.device)
+        out = torch.zeros(stacked.shape[1], dtype=torch.float64,
+                          device=stacked.device)
+        for k in range(stacked.shape[0]):
+            s = s + a[k]
+            out += a[k] * stacked[k]
+        return out * (1.0 / s)
+
+    def agg_geomed(self, stacked):
+        """Smoothed-Weiszfeld geometric median of the updates (module
+        docstring), fp64.  Remembers the normalised weights in
+        last_weights."""
+        a = self.geomed_weights(stacked)
+        self.last_weights = a / a.sum()
+        if _gpu(stacked):
+            return ext().agg_avg(stacked, a)
+        return self._geomed_mean(stacked, a)
+
+    def _log_geomed(self, agent_ids, cur_round):
+        if self.writer:
+            bad = [p for p, i in enumerate(agent_ids)
+                   if i < self.args.num_corrupt]
+            share = float(self.last_weights[bad].sum()) if bad else 0.0
+            self.writer.add_scalar('Geomed/Corrupt_Weight', share, cur_round)
+
     def agg_sign(self, stacked):
         if _gpu(stacked):
             return ext().agg_sign(stacked)
@@ -347,6 +432,8 @@ class Aggregation:
                else buffer_deltas[0].device)
         if self.args.aggr == 'krum':
             w = self._krum_weights(len(agent_ids), dev)
+        elif self.args.aggr == 'geomed':
+            w = self.last_weights.to(dev)
         else:
             w = self._weights(agent_ids, dev)
         if isinstance(buffer_deltas, list):

@@ -731,6 +731,51 @@ torch::Tensor pairwise_sqdist(torch::Tensor U) {
   return D;
 }
 
+// (K, n) fp64, contiguous, on device, 1 <= K <= geomed_max_k(), n >= 1.
+static void check_geomed(const torch::Tensor& U) {
+  CHK(U.is_cuda());
+  CHK(U.dim() == 2);
+  CHK(U.scalar_type() == torch::kFloat64);
+  CHK(U.is_contiguous());
+  CHK(U.size(0) >= 1 && U.size(0) <= geomed_max_k());
+  CHK(U.size(1) >= 1);
+}
+
+// d2[k] = ||U_k - z||^2, z the weighted mean of the rows under a (K fp64)
+torch::Tensor geomed_sqdist(torch::Tensor U, torch::Tensor a) {
+  check_geomed(U);
+  CHK(a.is_cuda() && a.device() == U.device());
+  CHK(a.dim() == 1 && a.numel() == U.size(0));
+  CHK(a.scalar_type() == torch::kFloat64);
+  CHK(a.is_contiguous());
+  int K = U.size(0);
+  long n = U.size(1);
+  auto ws = torch::empty({geomed_ws_doubles(K, n)}, U.options());
+  auto d2 = torch::empty({K}, U.options());
+  launch_geomed_sqdist(U.data_ptr<double>(), a.data_ptr<double>(), K, n,
+                       ws.data_ptr<double>(), d2.data_ptr<double>(),
+                       stream_of(U));
+  return d2;
+}
+
+// (a, d2) after `iters` Weiszfeld updates from a = ones
+std::tuple<torch::Tensor, torch::Tensor> geomed_weights(torch::Tensor U,
+                                                        int64_t iters,
+                                                        double nu) {
+  check_geomed(U);
+  CHK(iters >= 0);
+  CHK(nu > 0.0);
+  int K = U.size(0);
+  long n = U.size(1);
+  auto ws = torch::empty({geomed_ws_doubles(K, n)}, U.options());
+  auto a = torch::empty({K}, U.options());
+  auto d2 = torch::empty({K}, U.options());
+  launch_geomed_weights(U.data_ptr<double>(), K, n, (int)iters, nu,
+                        ws.data_ptr<double>(), a.data_ptr<double>(),
+                        d2.data_ptr<double>(), stream_of(U));
+  return {a, d2};
+}
+
 void apply_update(torch::Tensor params, torch::Tensor agg, torch::Tensor lr,
                   double slr) {
   CHK_CUDA(params);
@@ -1490,6 +1535,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pairdist_max_k", &pairdist_max_k);
   m.def("pairdist_chunks", &pairdist_chunks);
   m.def("pairdist_ws_doubles", &pairdist_ws_doubles);
+  m.def("geomed_sqdist", &geomed_sqdist);
+  m.def("geomed_weights", &geomed_weights);
+  m.def("geomed_max_k", &geomed_max_k);
+  m.def("geomed_chunks", &geomed_chunks);
+  m.def("geomed_ws_doubles", &geomed_ws_doubles);
   m.def("add_noise", &add_noise);
   m.def("gemm", &gemm);
   m.def("gemm_bf16", &gemm_bf16);

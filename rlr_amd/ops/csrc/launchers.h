@@ -251,6 +251,23 @@ int pairdist_chunks(int K, long n);
 long pairdist_ws_doubles(int K, long n);
 void launch_pairwise_sqdist(const double* U, int K, long n, double* ws,
                             double* D, void* s);
+// geomed.hip: smoothed Weiszfeld iterations for the geometric median of the
+// rows of U (K, n), 1 <= K <= geomed_max_k().  Stage 1 splits n into
+// geomed_chunks(K, n) <= 512 chunks (a pure function of K and n) and writes
+// one partial squared distance per (chunk, k) to ws[chunk][K]; 1 / sum a
+// lives behind the partials.  launch_geomed_sqdist: d2[k] = ||U_k - z||^2
+// for the weighted mean z under a caller-given a (K).
+// launch_geomed_weights: a = ones, then iters x (distances, a = 1 / max(nu,
+// sqrt(d2))) with no host synchronisation; d2 = the last distances (zeros
+// for iters == 0).
+int geomed_max_k();
+int geomed_chunks(int K, long n);
+long geomed_ws_doubles(int K, long n);
+void launch_geomed_sqdist(const double* U, const double* a, int K, long n,
+                          double* ws, double* d2, void* s);
+void launch_geomed_weights(const double* U, int K, long n, int iters,
+                           double nu, double* ws, double* a, double* d2,
+                           void* s);
 // gemm_f32.hip
 int gemm_f32_splitk(int M, int N, int K);
 long gemm_splitk_ws_floats(int M, int N, int SK);

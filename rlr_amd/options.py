@@ -28,9 +28,10 @@ def args_parser(argv=None):
     parser.add_argument('--rounds', type=int, default=200,
                         help="number of communication rounds R")
     parser.add_argument('--aggr', type=str, default='avg',
-                        choices=['avg', 'comed', 'sign', 'trmean', 'krum'],
-                        help="aggregation rule (trmean and krum are build "
-                             "additions)")
+                        choices=['avg', 'comed', 'sign', 'trmean', 'krum',
+                                 'geomed'],
+                        help="aggregation rule (trmean, krum and geomed are "
+                             "build additions)")
     parser.add_argument('--local_ep', type=int, default=2,
                         help="number of local epochs E")
     parser.add_argument('--bs', type=int, default=256,
@@ -75,6 +76,12 @@ def args_parser(argv=None):
     parser.add_argument('--krum_m', type=int, default=0,
                         help="number of agents Krum keeps: 1 = classic Krum, "
                              "0 = K - krum_f (Multi-Krum)")
+    parser.add_argument('--geomed_iters', type=int, default=8,
+                        help="smoothed Weiszfeld iterations; 0 = the "
+                             "unweighted mean (--aggr geomed)")
+    parser.add_argument('--geomed_nu', type=float, default=1e-6,
+                        help="smoothing: a weight is 1 / max(nu, distance) "
+                             "(--aggr geomed)")
     parser.add_argument('--seed', type=int, default=42,
                         help="master seed; all RNG streams derive from it "
                              "world-size-invariantly")
@@ -118,7 +125,7 @@ def finalize_args(args):
     (reference federated.py:23); 0 <= trim_frac < 0.5 so that at least one
     value per coordinate survives the trim for every K; krum_f, krum_m >= 0
     (their upper limits depend on the sampled K and are checked by the
-    server)."""
+    server); geomed_iters >= 0 and geomed_nu > 0."""
     args.server_lr = args.server_lr if args.aggr == 'sign' else 1.0
     if not 0 <= args.trim_frac < 0.5:
         raise ValueError(
@@ -127,6 +134,11 @@ def finalize_args(args):
         raise ValueError(
             f"--krum_f and --krum_m must be >= 0, got {args.krum_f} and "
             f"{args.krum_m}")
+    if args.geomed_iters < 0:
+        raise ValueError(
+            f"--geomed_iters must be >= 0, got {args.geomed_iters}")
+    if not args.geomed_nu > 0:
+        raise ValueError(f"--geomed_nu must be > 0, got {args.geomed_nu}")
     if args.device is None:
         import torch
         if torch.cuda.is_available():

@@ -7,9 +7,9 @@ from time import ctime
 
 
 def run_name(args):
-    """Reference federated.py:27-30 run-name string; the trimmed mean and
-    krum (build additions) append their own flags, every other rule keeps
-    the reference name byte for byte."""
+    """Reference federated.py:27-30 run-name string; the trimmed mean, krum
+    and geomed (build additions) append their own flags, every other rule
+    keeps the reference name byte for byte."""
     name = (f"time:{ctime()}-clip_val:{args.clip}-noise_std:{args.noise}"
             f"-aggr:{args.aggr}-s_lr:{args.server_lr}-num_cor:{args.num_corrupt}"
             f"thrs_robustLR:{args.robustLR_threshold}"
@@ -18,6 +18,8 @@ def run_name(args):
         name += f"-trim:{args.trim_frac}"
     if args.aggr == 'krum':
         name += f"-krum_f:{args.krum_f}-krum_m:{args.krum_m}"
+    if args.aggr == 'geomed':
+        name += f"-gm_iters:{args.geomed_iters}-gm_nu:{args.geomed_nu}"
     return name
 
 
@@ -41,6 +43,9 @@ def print_exp_details(args):
         print(f'    Trim Fraction: {args.trim_frac}')
     if args.aggr == 'krum':
         print(f'    Krum f / m: {args.krum_f} / {args.krum_m}')
+    if args.aggr == 'geomed':
+        print(f'    Geomed iters / nu: {args.geomed_iters} / '
+              f'{args.geomed_nu}')
     print(f'    Number of agents: {args.num_agents}')
     print(f'    Fraction of agents: {args.agent_frac}')
     print(f'    Batch size: {args.bs}')
