@@ -10,7 +10,10 @@ coordinate-wise trimmed mean (--aggr trmean, Yin et al. 2018), sharing one
 LDS sorting-network kernel family with the median at more than 64 sampled
 agents, Krum / Multi-Krum (--aggr krum, Blanchard et al. 2017) on an
 fp64 MFMA pairwise-distance kernel, and the geometric median / RFA
-(--aggr geomed, Pillutla et al.) on a fused Weiszfeld distance kernel.
+(--aggr geomed, Pillutla et al.) on a fused Weiszfeld distance kernel; in
+front of every rule, server-side norm clipping (--server_clip, Sun et al.)
+on a streaming row-norm kernel, and the boosted model-replacement attack
+(--attack_boost, Bagdasaryan et al.) it is the baseline defence against.
 
 Architecture (nothing here is a port):
   * one process per GPU; sampled agents are sharded contiguously across

@@ -9,6 +9,11 @@ Behavior-compatible semantics, MI355X-native execution:
     (agent.py:37), per-batch grad-norm clip 10 + SGD step (fused kernel),
     per-BATCH PGD projection when clip>0 (agent.py:53-60 — inside the batch
     loop, not per-epoch), fp64 flat update return (agent.py:62-64).
+  * --attack_boost b != 1 (build addition; model replacement, Bagdasaryan
+    et al., "How To Backdoor Federated Learning"): a corrupt agent returns
+    b times its fp64 update and BatchNorm buffer delta.  The multiply comes
+    after the last PGD projection, so the boosted update leaves the
+    client's clip ball; b = 1 runs exactly the code it ran before.
   * all RNG (poison-index choice, epoch shuffling, dropout) comes from
     per-(agent, round, ...) derived streams, so results are independent of
     which rank trains the agent (world-size invariance)."""
@@ -130,4 +135,11 @@ class Agent:
         if buf0 is not None:
             self.buffer_delta = gm.flat_buffers - buf0
             gm.flat_buffers.copy_(buf0)
+        # model replacement (Bagdasaryan et al.): a corrupt agent boosts what
+        # it sends, AFTER its own PGD projection, which it thereby escapes
+        boost = getattr(args, 'attack_boost', 1.0)
+        if boost != 1.0 and self.id < args.num_corrupt:
+            update = update * boost
+            if buf0 is not None:
+                self.buffer_delta = self.buffer_delta * boost
         return update

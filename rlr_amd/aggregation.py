@@ -63,8 +63,30 @@ Rules (each a HIP kernel on the GPU path, ops/csrc/aggregation.hip):
     on the GPU); each is a pure function of its input.  last_weights holds
     the final a normalised to sum 1.
   * sign (aggregation.py:71-75): sign(sum_k sign(U_k)).
+  * server-side norm clipping (build addition, --server_clip > 0; Sun et
+    al., "Can You Really Backdoor Federated Learning?", and the clipping
+    half of DP-FedAvg): a stage IN FRONT of every rule above.
+        norm[k] = sqrt(sum_j U[k][j]^2)               fp64
+        tau     = server_clip                         --server_clip_mode fixed
+        tau     = server_clip * lower median of norm  median: the
+                  ((K-1)/2)-th smallest, as comed takes it
+        s[k]    = norm[k] > tau ? tau / norm[k] : 1.0
+        C[k][j] = s[k] * U[k][j]                      one rounding each
+    Every rule sees C: avg, comed, sign, trmean, krum's distances and
+    selection, geomed's weights, and the RLR vote (unchanged: s > 0 keeps
+    every sign).  A zero row and a row with norm == tau keep s = 1 and
+    their bits.  On the GPU ops/csrc/rowclip.hip (any K, three launches, no
+    host sync) scales the matrix in place; CPU and force_eager build C in
+    plain torch.  The backends agree to rounding (the sum over n is chunked
+    on the GPU): norm and fixed-mode s to (n + 4) 2^-52 relative, median-
+    mode tau and s to twice that (PARITY.md).  BatchNorm buffer deltas are
+    multiplied by the same s[k] before their mean.  last_clip_scale,
+    last_clip_bound and last_norms hold s, tau and norm.  The older
+    clip_updates below stays the disconnected reference-parity stub.
   * optional N(0, noise*clip) gaussian noise (aggregation.py:34-35) from a
-    per-round derived stream.  NOTE: the fused GPU avg path draws noise
+    per-round derived stream; N(0, noise*server_clip) under a fixed
+    --server_clip, whose bound is then the sensitivity (median mode keeps
+    noise*clip: its bound is data-dependent and lives on the device).  NOTE: the fused GPU avg path draws noise
     from the on-device philox Box-Muller stream, while the CPU and
     comed/sign paths draw from a torch CPU generator — the same
     seed+config yields a DIFFERENT (but equally deterministic) noise
@@ -96,19 +118,31 @@ class Aggregation:
         self.cum_net_mov = 0.0
         self.last_selected = None   # krum: sampled positions kept last round
         self.last_weights = None    # geomed: final weights, normalised
+        # server_clip: last round's factors s (K), bound tau (0-d) and
+        # pre-clip norms (K), on the updates' device
+        self.last_clip_scale = None
+        self.last_clip_bound = None
+        self.last_norms = None
 
     # ------------------------------------------------------------- entry
 
     def aggregate_updates(self, global_model, agent_updates, cur_round,
                           agent_ids=None):
         """agent_updates: dict {agent_id: fp64 vec} (reference API) or a
-        stacked (S, n) fp64 tensor with agent_ids giving the sampled order."""
+        stacked (S, n) fp64 tensor with agent_ids giving the sampled order.
+        With --server_clip a stacked matrix on the GPU is clipped IN PLACE;
+        the dict form is stacked into a copy first, so the caller's tensors
+        are untouched, as is a matrix on the CPU."""
         if isinstance(agent_updates, dict):
             agent_ids = list(agent_updates.keys())
             stacked = torch.stack([agent_updates[i] for i in agent_ids])
         else:
             stacked = agent_updates
             assert agent_ids is not None
+
+        if self._server_clip() > 0:
+            stacked = self.server_clip_updates(stacked)
+            self._log_clip(agent_ids, cur_round)
 
         krum = self.args.aggr == 'krum'
         if krum:
@@ -130,8 +164,7 @@ class Aggregation:
             w = (self._krum_weights(stacked.shape[0], stacked.device) if krum
                  else a if geomed
                  else self._weights(agent_ids, stacked.device))
-            noise_std = (self.args.noise * self.args.clip
-                         if self.args.noise > 0 else 0.0)
+            noise_std = self._noise_std() if self.args.noise > 0 else 0.0
             seed = derive_seed(self.args.seed, 'noise', cur_round)
             ext().fused_avg_rlr_apply(
                 stacked, w, global_model.flat_params,
@@ -181,6 +214,54 @@ class Aggregation:
             agg = agg + self._noise(cur_round, agg.device, agg.dtype)
 
         self._apply(global_model, lr_vector, agg)
+
+    # ------------------------------------------------------- server clip
+
+    def _server_clip(self):
+        return float(getattr(self.args, 'server_clip', 0.0))
+
+    def _server_clip_mode(self):
+        return getattr(self.args, 'server_clip_mode', 'fixed')
+
+    def server_clip_updates(self, stacked):
+        """The clipped matrix C[k] = s[k] * U[k] (module docstring); on the
+        GPU `stacked` itself, scaled in place.  Remembers s, tau and the
+        pre-clip norms in last_clip_scale / last_clip_bound / last_norms."""
+        value = self._server_clip()
+        mode = self._server_clip_mode()
+        if not value >= 0 or mode not in ('fixed', 'median'):
+            raise ValueError(
+                f"server_clip={value} must be >= 0 and server_clip_mode="
+                f"{mode} one of fixed, median")
+        if _gpu(stacked):
+            s, norm, tau = ext().rowclip_(stacked, value, mode == 'median')
+        else:
+            K = stacked.shape[0]
+            norm = torch.sqrt((stacked * stacked).sum(1))
+            if mode == 'median':
+                tau = value * torch.sort(norm).values[(K - 1) // 2]
+            else:
+                tau = torch.tensor(value, dtype=torch.float64,
+                                   device=stacked.device)
+            s = torch.where(norm > tau, tau / norm, torch.ones_like(norm))
+            stacked = s.unsqueeze(1) * stacked
+        self.last_clip_scale, self.last_clip_bound = s, tau
+        self.last_norms = norm
+        return stacked
+
+    def _log_clip(self, agent_ids, cur_round):
+        if self.writer:
+            s = self.last_clip_scale.cpu()
+            bad = [p for p, i in enumerate(agent_ids)
+                   if i < self.args.num_corrupt]
+            self.writer.add_scalar('Clip/Bound', float(self.last_clip_bound),
+                                   cur_round)
+            self.writer.add_scalar('Clip/Frac_Clipped',
+                                   float((s < 1.0).double().mean()),
+                                   cur_round)
+            self.writer.add_scalar('Clip/Corrupt_Scale_Mean',
+                                   float(s[bad].mean()) if bad else 1.0,
+                                   cur_round)
 
     # ------------------------------------------------------------- rules
 
@@ -399,9 +480,18 @@ class Aggregation:
             return ext().agg_sign(stacked)
         return torch.sign(torch.sign(stacked).sum(dim=0))
 
+    def _noise_std(self):
+        """noise * server_clip when the server enforces a fixed bound (its
+        bound is then the sensitivity: clip + noise is DP-FedAvg), noise *
+        clip otherwise — also in median mode, whose bound lives on the
+        device and changes with the data."""
+        if self._server_clip() > 0 and self._server_clip_mode() == 'fixed':
+            return self.args.noise * self._server_clip()
+        return self.args.noise * self.args.clip
+
     def _noise(self, cur_round, device, dtype):
         g = torch_gen(self.args.seed, 'noise', cur_round)
-        n = torch.normal(mean=0.0, std=self.args.noise * self.args.clip,
+        n = torch.normal(mean=0.0, std=self._noise_std(),
                          size=(self.n_params,), generator=g)
         return n.to(device=device, dtype=dtype)
 
@@ -423,7 +513,9 @@ class Aggregation:
     def aggregate_buffers(self, global_model, buffer_deltas, agent_ids):
         """FedAvg-BN: data-weighted mean of BatchNorm running-stat deltas
         (build extension — the reference has no BN).  Under krum: the
-        unweighted mean over the agents selected for the parameters."""
+        unweighted mean over the agents selected for the parameters.  Under
+        --server_clip agent k's delta is first multiplied by the s[k] its
+        update was clipped with."""
         if global_model.n_buffers == 0 or buffer_deltas is None:
             return
         if isinstance(buffer_deltas, (list, tuple)) and not buffer_deltas:
@@ -438,6 +530,10 @@ class Aggregation:
             w = self._weights(agent_ids, dev)
         if isinstance(buffer_deltas, list):
             buffer_deltas = torch.stack(buffer_deltas)
+        if self._server_clip() > 0 and self.last_clip_scale is not None:
+            # an agent's buffer delta shrinks with its update
+            buffer_deltas = (buffer_deltas.double()
+                             * self.last_clip_scale.to(dev).unsqueeze(1))
         if _gpu(buffer_deltas):
             # same weighted-mean HIP kernel as the parameter path (the
             # buffer matrix is tiny — K x ~10k — so the fp64 round-trip

@@ -776,6 +776,73 @@ std::tuple<torch::Tensor, torch::Tensor> geomed_weights(torch::Tensor U,
   return {a, d2};
 }
 
+// (K, n) fp64, contiguous, on device, K >= 1, n >= 1: no upper limit on K.
+static void check_rowclip(const torch::Tensor& U) {
+  CHK(U.is_cuda());
+  CHK(U.dim() == 2);
+  CHK(U.scalar_type() == torch::kFloat64);
+  CHK(U.is_contiguous());
+  CHK(U.size(0) >= 1 && U.size(0) <= INT32_MAX);
+  CHK(U.size(1) >= 1);
+}
+
+// the caller's workspace (at least rownorm_ws_doubles(K, n) doubles), or a
+// fresh one of exactly that size
+static torch::Tensor rowclip_ws(const torch::Tensor& U,
+                                const c10::optional<torch::Tensor>& ws) {
+  const long need = rownorm_ws_doubles((int)U.size(0), U.size(1));
+  if (!ws.has_value()) return torch::empty({need}, U.options());
+  const torch::Tensor& w = *ws;
+  CHK(w.is_cuda() && w.device() == U.device());
+  CHK(w.scalar_type() == torch::kFloat64);
+  CHK(w.dim() == 1 && w.is_contiguous());
+  CHK(w.numel() >= need);
+  return w;
+}
+
+// stage 1 alone: the (chunks, K) partial sums of squares
+torch::Tensor rownorm_partials(torch::Tensor U) {
+  check_rowclip(U);
+  int K = U.size(0);
+  long n = U.size(1);
+  auto ws = torch::empty({(long)rownorm_chunks(K, n), (long)K}, U.options());
+  launch_rownorm_partials(U.data_ptr<double>(), K, n, ws.data_ptr<double>(),
+                          stream_of(U));
+  return ws;
+}
+
+// norm[k] = ||U_k||_2
+torch::Tensor row_norms(torch::Tensor U, c10::optional<torch::Tensor> ws) {
+  check_rowclip(U);
+  int K = U.size(0);
+  long n = U.size(1);
+  auto w = rowclip_ws(U, ws);
+  auto norm = torch::empty({K}, U.options());
+  launch_row_norms(U.data_ptr<double>(), K, n, w.data_ptr<double>(),
+                   norm.data_ptr<double>(), stream_of(U));
+  return norm;
+}
+
+// U[k] *= s[k] in place; (s, norm, tau).  tau = value, or value * the lower
+// median of the norms in median mode
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> rowclip_(
+    torch::Tensor U, double value, bool median_mode,
+    c10::optional<torch::Tensor> ws) {
+  check_rowclip(U);
+  CHK(value >= 0.0);
+  int K = U.size(0);
+  long n = U.size(1);
+  auto w = rowclip_ws(U, ws);
+  auto norm = torch::empty({K}, U.options());
+  auto scale = torch::empty({K}, U.options());
+  auto tau = torch::empty({}, U.options());
+  launch_rowclip(U.data_ptr<double>(), K, n, value, median_mode ? 1 : 0,
+                 w.data_ptr<double>(), norm.data_ptr<double>(),
+                 scale.data_ptr<double>(), tau.data_ptr<double>(),
+                 stream_of(U));
+  return {scale, norm, tau};
+}
+
 void apply_update(torch::Tensor params, torch::Tensor agg, torch::Tensor lr,
                   double slr) {
   CHK_CUDA(params);
@@ -1540,6 +1607,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("geomed_max_k", &geomed_max_k);
   m.def("geomed_chunks", &geomed_chunks);
   m.def("geomed_ws_doubles", &geomed_ws_doubles);
+  m.def("rownorm_partials", &rownorm_partials);
+  m.def("row_norms", &row_norms, py::arg("U"), py::arg("ws") = py::none());
+  m.def("rowclip_", &rowclip_, py::arg("U"), py::arg("value"),
+        py::arg("median_mode"), py::arg("ws") = py::none());
+  m.def("rownorm_chunks", &rownorm_chunks);
+  m.def("rownorm_ws_doubles", &rownorm_ws_doubles);
   m.def("add_noise", &add_noise);
   m.def("gemm", &gemm);
   m.def("gemm_bf16", &gemm_bf16);

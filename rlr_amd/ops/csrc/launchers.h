@@ -268,6 +268,23 @@ void launch_geomed_sqdist(const double* U, const double* a, int K, long n,
 void launch_geomed_weights(const double* U, int K, long n, int iters,
                            double nu, double* ws, double* a, double* d2,
                            void* s);
+// rowclip.hip: L2 norms of the rows of U (K, n) and the server-side clip
+// U[k] *= s[k], s[k] = norm[k] > tau ? tau / norm[k] : 1, for any K >= 1.
+// Stage 1 splits n into rownorm_chunks(K, n) chunks (a pure function of K
+// and n) and writes one partial sum of squares per (chunk, k) to
+// ws[chunk][K].  launch_rownorm_partials is stage 1 alone, launch_row_norms
+// adds the one-block reduction to norm (K).  launch_rowclip: tau = value
+// (median_mode == 0) or value * the lower median of the norms; writes norm
+// (K), scale (K) and *tau, then scales U in place; no host synchronisation.
+int rownorm_chunks(int K, long n);
+long rownorm_ws_doubles(int K, long n);
+void launch_rownorm_partials(const double* U, int K, long n, double* ws,
+                             void* s);
+void launch_row_norms(const double* U, int K, long n, double* ws,
+                      double* norm, void* s);
+void launch_rowclip(double* U, int K, long n, double value, int median_mode,
+                    double* ws, double* norm, double* scale, double* tau,
+                    void* s);
 // gemm_f32.hip
 int gemm_f32_splitk(int M, int N, int K);
 long gemm_splitk_ws_floats(int M, int N, int SK);

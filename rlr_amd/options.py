@@ -1,7 +1,9 @@
 """CLI — reproduces the reference's full 21-flag surface
 (reference: src/options.py:4-74) plus infrastructure flags that the
 MI355X build adds (--seed, --ckpt_dir, --resume, --synthetic, --dtype,
---agents_per_stream, --no_tb).
+--agents_per_stream, --no_tb), its aggregation rules and their flags, the
+server-side norm clip (--server_clip, --server_clip_mode) and the boosted
+attack (--attack_boost).
 
 Notes kept behavior-compatible with the reference:
   * default base_class is 5 (options.py:40 — the README's claim of 1 is
@@ -11,6 +13,8 @@ Notes kept behavior-compatible with the reference:
 """
 
 import argparse
+
+SERVER_CLIP_MODES = ('fixed', 'median')
 
 
 def args_parser(argv=None):
@@ -82,6 +86,17 @@ def args_parser(argv=None):
     parser.add_argument('--geomed_nu', type=float, default=1e-6,
                         help="smoothing: a weight is 1 / max(nu, distance) "
                              "(--aggr geomed)")
+    parser.add_argument('--server_clip', type=float, default=0,
+                        help="server-side bound on each update's L2 norm "
+                             "before aggregation (0 disables)")
+    parser.add_argument('--server_clip_mode', type=str, default='fixed',
+                        choices=list(SERVER_CLIP_MODES),
+                        help="fixed: --server_clip is the bound; median: it "
+                             "multiplies the median norm of the round's "
+                             "sampled updates")
+    parser.add_argument('--attack_boost', type=float, default=1.0,
+                        help="corrupt agents multiply their update by this "
+                             "before sending it (model replacement)")
     parser.add_argument('--seed', type=int, default=42,
                         help="master seed; all RNG streams derive from it "
                              "world-size-invariantly")
@@ -125,7 +140,8 @@ def finalize_args(args):
     (reference federated.py:23); 0 <= trim_frac < 0.5 so that at least one
     value per coordinate survives the trim for every K; krum_f, krum_m >= 0
     (their upper limits depend on the sampled K and are checked by the
-    server); geomed_iters >= 0 and geomed_nu > 0."""
+    server); geomed_iters >= 0 and geomed_nu > 0; server_clip >= 0 with a
+    known mode; attack_boost > 0."""
     args.server_lr = args.server_lr if args.aggr == 'sign' else 1.0
     if not 0 <= args.trim_frac < 0.5:
         raise ValueError(
@@ -139,6 +155,16 @@ def finalize_args(args):
             f"--geomed_iters must be >= 0, got {args.geomed_iters}")
     if not args.geomed_nu > 0:
         raise ValueError(f"--geomed_nu must be > 0, got {args.geomed_nu}")
+    if not args.server_clip >= 0:
+        raise ValueError(
+            f"--server_clip must be >= 0, got {args.server_clip}")
+    if args.server_clip_mode not in SERVER_CLIP_MODES:
+        raise ValueError(
+            f"--server_clip_mode must be one of {SERVER_CLIP_MODES}, got "
+            f"{args.server_clip_mode}")
+    if not 0 < args.attack_boost < float('inf'):
+        raise ValueError(
+            f"--attack_boost must be > 0, got {args.attack_boost}")
     if args.device is None:
         import torch
         if torch.cuda.is_available():
