@@ -78,20 +78,17 @@ Rules (each a HIP kernel on the GPU path, ops/csrc/aggregation.hip):
     their bits.  On the GPU ops/csrc/rowclip.hip (any K, three launches, no
     host sync) scales the matrix in place; CPU and force_eager build C in
     plain torch.  The backends agree to rounding (the sum over n is chunked
-    on the GPU): norm and fixed-mode s to (n + 4) 2^-52 relative, median-
-    mode tau and s to twice that (PARITY.md).  BatchNorm buffer deltas are
+    on the GPU; bounds in PARITY.md).  BatchNorm buffer deltas are
     multiplied by the same s[k] before their mean.  last_clip_scale,
     last_clip_bound and last_norms hold s, tau and norm.  The older
     clip_updates below stays the disconnected reference-parity stub.
   * optional N(0, noise*clip) gaussian noise (aggregation.py:34-35) from a
     per-round derived stream; N(0, noise*server_clip) under a fixed
     --server_clip, whose bound is then the sensitivity (median mode keeps
-    noise*clip: its bound is data-dependent and lives on the device).  NOTE: the fused GPU avg path draws noise
-    from the on-device philox Box-Muller stream, while the CPU and
-    comed/sign paths draw from a torch CPU generator — the same
-    seed+config yields a DIFFERENT (but equally deterministic) noise
-    realization across the two backends.  Each backend is reproducible
-    and world-size-invariant on its own; see PARITY.md.
+    noise*clip: its bound is data-dependent and lives on the device).  The
+    fused GPU avg path draws from the on-device philox stream, every other
+    path from a torch CPU generator: a different, equally deterministic
+    realization per backend (PARITY.md).
   * fused apply (aggregation.py:38-40): theta <- float32(theta + lr * agg).
 """
 
@@ -99,11 +96,22 @@ import torch
 from torch.nn import functional as F
 
 from .ops import ext, force_eager
-from .utils.rng import torch_gen
+from .options import check_geomed, check_server_clip
+from .utils.rng import derive_seed, torch_gen
 
 
 def _gpu(t):
     return t.is_cuda and not force_eager()
+
+
+def _row_sum(rows, w=None):
+    """sum_k w[k] * rows[k] (w omitted: sum_k rows[k]) — THE sequential sum
+    of the CPU rules, which PARITY.md's bit-for-bit statements rest on:
+    from zeros, added in place, in ascending k."""
+    out = torch.zeros(rows.shape[1], dtype=torch.float64, device=rows.device)
+    for k in range(rows.shape[0]):
+        out += rows[k] if w is None else w[k] * rows[k]
+    return out
 
 
 class Aggregation:
@@ -144,76 +152,69 @@ class Aggregation:
             stacked = self.server_clip_updates(stacked)
             self._log_clip(agent_ids, cur_round)
 
-        krum = self.args.aggr == 'krum'
-        if krum:
-            self.last_selected = self.krum_select(stacked)
-            self._log_krum(agent_ids, cur_round)
+        rule, w, span = self._resolve(stacked, agent_ids, cur_round)
+        K = stacked.shape[0]
+        rlr = self.args.robustLR_threshold > 0
 
-        geomed = self.args.aggr == 'geomed'
-        if geomed:
-            a = self.geomed_weights(stacked)
-            self.last_weights = a / a.sum()
-            self._log_geomed(agent_ids, cur_round)
-
-        if _gpu(stacked) and (self.args.aggr == 'avg' or krum or geomed):
+        if _gpu(stacked) and w is not None:
             # headline path: ONE fused kernel does sign-vote + weighted avg
             # + noise + fp32 apply in a single pass over the K x n matrix
-            # (krum: 0/1 weights over the selection, geomed: the Weiszfeld
-            # weights; vote over all K)
-            from .utils.rng import derive_seed
-            w = (self._krum_weights(stacked.shape[0], stacked.device) if krum
-                 else a if geomed
-                 else self._weights(agent_ids, stacked.device))
+            # (vote over all K, whatever the weights)
             noise_std = self._noise_std() if self.args.noise > 0 else 0.0
             seed = derive_seed(self.args.seed, 'noise', cur_round)
             ext().fused_avg_rlr_apply(
-                stacked, w, global_model.flat_params,
-                self.args.robustLR_threshold > 0,
+                stacked, w, global_model.flat_params, rlr,
                 float(self.args.robustLR_threshold), float(self.server_lr),
                 float(noise_std), seed, 0, False)
             return
 
-        if _gpu(stacked) and self.args.noise == 0:
+        if (_gpu(stacked) and span is not None and self.args.noise == 0
+                and K <= ext().orderstat_max_k()
+                and (self.args.aggr == 'trmean' or K > 64)):
             # order-statistic rules: ONE fused kernel sorts each column in
-            # LDS, takes the vote from the resident tile and applies
-            K = stacked.shape[0]
-            span = None
-            if self.args.aggr == 'trmean':
-                b = self._trim_count(K)
-                span = (b, K - b)
-            elif self.args.aggr == 'comed' and K > 64:
-                span = ((K - 1) // 2, (K - 1) // 2 + 1)
-            if span is not None and K <= ext().orderstat_max_k():
-                ext().orderstat_rlr_apply(
-                    stacked, span[0], span[1], global_model.flat_params,
-                    self.args.robustLR_threshold > 0,
-                    float(self.args.robustLR_threshold),
-                    float(self.server_lr), False)
-                return
+            # LDS, takes the vote from the resident tile and applies.  The
+            # median of K <= 64 stays composed: its count-and-pick kernel
+            # is the faster one there (docs/KERNELS.md)
+            ext().orderstat_rlr_apply(
+                stacked, span[0], span[1], global_model.flat_params, rlr,
+                float(self.args.robustLR_threshold), float(self.server_lr),
+                False)
+            return
 
-        lr_vector = None
-        if self.args.robustLR_threshold > 0:
-            lr_vector = self.compute_robustLR(stacked)
-
-        if self.args.aggr == 'avg':
-            agg = self.agg_avg(stacked, agent_ids)
-        elif self.args.aggr == 'comed':
-            agg = self.agg_comed(stacked)
-        elif self.args.aggr == 'trmean':
-            agg = self.agg_trmean(stacked)
-        elif self.args.aggr == 'sign':
-            agg = self.agg_sign(stacked)
-        elif krum:
-            agg = self._krum_mean(stacked, self.last_selected)
-        elif geomed:
-            agg = self._geomed_mean(stacked, a)
-        else:
-            raise ValueError(self.args.aggr)
-
+        # composed path: vote, rule, noise, apply
+        lr_vector = self.compute_robustLR(stacked) if rlr else None
+        agg = rule(stacked)
         if self.args.noise > 0:
             agg = agg + self._noise(cur_round, agg.device, agg.dtype)
-
         self._apply(global_model, lr_vector, agg)
+
+    def _resolve(self, stacked, agent_ids, cur_round):
+        """What --aggr decides for this round, looked at in this one place:
+        (rule, weights, span).  weights: for a weighted mean of the rows;
+        span: [lo, hi) of each sorted column to average; neither for sign.
+        rule(stacked) is the aggregate as the composed path computes it.
+        Sets last_selected / last_weights and logs what the rule chose."""
+        aggr, K, dev = self.args.aggr, stacked.shape[0], stacked.device
+        if aggr == 'avg':
+            w = self._weights(agent_ids, dev)
+            return (lambda U: self._mean(U, w, self._avg_mean)), w, None
+        if aggr == 'krum':
+            self.last_selected = self.krum_select(stacked)
+            self._log_krum(agent_ids, cur_round)
+            w = self._krum_weights(K, dev)
+            return (lambda U: self._mean(U, w, self._krum_mean)), w, None
+        if aggr == 'geomed':
+            a = self.geomed_weights(stacked)
+            self.last_weights = a / a.sum()
+            self._log_geomed(agent_ids, cur_round)
+            return (lambda U: self._mean(U, a, self._geomed_mean)), a, None
+        if aggr == 'comed':
+            return self.agg_comed, None, self._comed_span(K)
+        if aggr == 'trmean':
+            return self.agg_trmean, None, self._trim_span(K)
+        if aggr == 'sign':
+            return self.agg_sign, None, None
+        raise ValueError(aggr)
 
     # ------------------------------------------------------- server clip
 
@@ -229,10 +230,7 @@ class Aggregation:
         pre-clip norms in last_clip_scale / last_clip_bound / last_norms."""
         value = self._server_clip()
         mode = self._server_clip_mode()
-        if not value >= 0 or mode not in ('fixed', 'median'):
-            raise ValueError(
-                f"server_clip={value} must be >= 0 and server_clip_mode="
-                f"{mode} one of fixed, median")
+        check_server_clip(value, mode)
         if _gpu(stacked):
             s, norm, tau = ext().rowclip_(stacked, value, mode == 'median')
         else:
@@ -280,16 +278,27 @@ class Aggregation:
                          dtype=torch.float64, device=device)
         return w
 
+    @staticmethod
+    def _mean(stacked, w, cpu_mean):
+        """Mean of the rows under the weights w: the agg_avg kernel, or in
+        plain torch one of the three cpu_mean below.  They differ only in
+        how they divide, in the last bit; PARITY.md pins each."""
+        return (ext().agg_avg(stacked, w) if _gpu(stacked)
+                else cpu_mean(stacked, w))
+
+    @staticmethod
+    def _avg_mean(stacked, w):
+        # summed in sampled order (world-size invariant)
+        return _row_sum(stacked, w) / w.sum()
+
     def agg_avg(self, stacked, agent_ids):
-        w = self._weights(agent_ids, stacked.device)
-        if _gpu(stacked):
-            return ext().agg_avg(stacked, w)
-        # sequential accumulation in sampled order (ws-invariant)
-        out = torch.zeros(stacked.shape[1], dtype=torch.float64,
-                          device=stacked.device)
-        for k in range(stacked.shape[0]):
-            out += w[k] * stacked[k]
-        return out / w.sum()
+        return self._mean(stacked, self._weights(agent_ids, stacked.device),
+                          self._avg_mean)
+
+    @staticmethod
+    def _comed_span(K):
+        """The lower median, torch.median's: sorted element (K - 1) // 2."""
+        return (K - 1) // 2, (K - 1) // 2 + 1
 
     def agg_comed(self, stacked):
         # the count-and-pick kernel re-reads the column K times per value
@@ -301,9 +310,8 @@ class Aggregation:
             if K <= 64:
                 return ext().agg_comed(stacked)
             if K <= ext().orderstat_max_k():
-                m = (K - 1) // 2
-                return ext().agg_orderstat(stacked, m, m + 1, False,
-                                           0.0, 0.0)[0]
+                return ext().agg_orderstat(stacked, *self._comed_span(K),
+                                           False, 0.0, 0.0)[0]
         return torch.median(stacked, dim=0).values
 
     def _trim_count(self, K):
@@ -315,6 +323,10 @@ class Aggregation:
                 f"agents from each end and leaves nothing to average")
         return b
 
+    def _trim_span(self, K):
+        b = self._trim_count(K)
+        return b, K - b
+
     def agg_trmean(self, stacked):
         """Coordinate-wise trimmed mean (Yin et al., 2018), unweighted like
         comed: per coordinate sort the K values, drop b from each end and
@@ -323,15 +335,11 @@ class Aggregation:
         does exactly this, so CPU and GPU agree bit for bit and the result
         does not depend on the agent order."""
         K = stacked.shape[0]
-        b = self._trim_count(K)
+        lo, hi = self._trim_span(K)
         if _gpu(stacked) and K <= ext().orderstat_max_k():
-            return ext().agg_orderstat(stacked, b, K - b, False, 0.0, 0.0)[0]
-        kept = torch.sort(stacked, dim=0).values[b:K - b]
-        out = torch.zeros(stacked.shape[1], dtype=torch.float64,
-                          device=stacked.device)
-        for r in range(K - 2 * b):
-            out += kept[r]
-        return out * (1.0 / (K - 2 * b))
+            return ext().agg_orderstat(stacked, lo, hi, False, 0.0, 0.0)[0]
+        kept = torch.sort(stacked, dim=0).values[lo:hi]
+        return _row_sum(kept) * (1.0 / (hi - lo))
 
     # -------------------------------------------------------------- krum
 
@@ -379,11 +387,7 @@ class Aggregation:
             # D is symmetric: sorting its columns sorts its rows
             return ext().agg_orderstat(D.contiguous(), 1, c + 1, False,
                                        0.0, 0.0)[0]
-        srt = torch.sort(D, dim=0).values
-        out = torch.zeros(K, dtype=torch.float64, device=D.device)
-        for r in range(1, c + 1):
-            out += srt[r]
-        return out * (1.0 / c)
+        return _row_sum(torch.sort(D, dim=0).values[1:c + 1]) * (1.0 / c)
 
     def krum_select(self, stacked):
         """Sampled positions of the m lowest-score agents, ascending."""
@@ -397,23 +401,15 @@ class Aggregation:
         w[self.last_selected.to(device)] = 1.0
         return w
 
-    def _krum_mean(self, stacked, selected):
-        K = stacked.shape[0]
-        s = torch.zeros(K, dtype=torch.float64, device=stacked.device)
-        s[selected] = 1.0
-        if _gpu(stacked):
-            return ext().agg_avg(stacked, s)
-        out = torch.zeros(stacked.shape[1], dtype=torch.float64,
-                          device=stacked.device)
-        for k in range(K):
-            out += s[k] * stacked[k]
-        return out * (1.0 / selected.numel())
+    def _krum_mean(self, stacked, w):
+        return _row_sum(stacked, w) * (1.0 / self.last_selected.numel())
 
     def agg_krum(self, stacked):
         """Unweighted mean of the Krum-selected updates (module docstring).
         Remembers the selection in last_selected."""
         self.last_selected = self.krum_select(stacked)
-        return self._krum_mean(stacked, self.last_selected)
+        w = self._krum_weights(stacked.shape[0], stacked.device)
+        return self._mean(stacked, w, self._krum_mean)
 
     def _log_krum(self, agent_ids, cur_round):
         if self.writer:
@@ -436,10 +432,7 @@ class Aggregation:
     def geomed_weights(self, stacked):
         """Raw Weiszfeld weights a[k] = 1 / max(nu, ||U_k - z||) after
         geomed_iters updates from a = ones (ones for geomed_iters = 0)."""
-        if self.args.geomed_iters < 0 or not self.args.geomed_nu > 0:
-            raise ValueError(
-                f"geomed_iters={self.args.geomed_iters} must be >= 0 and "
-                f"geomed_nu={self.args.geomed_nu} must be > 0")
+        check_geomed(self.args.geomed_iters, self.args.geomed_nu)
         if _gpu(stacked) and stacked.shape[0] <= ext().geomed_max_k():
             return ext().geomed_weights(stacked, int(self.args.geomed_iters),
                                         float(self.args.geomed_nu))[0]
@@ -450,13 +443,8 @@ class Aggregation:
     @staticmethod
     def _geomed_mean(stacked, a):
         """(sum_k a[k] U[k]) * (1 / sum a), both sums sequential from 0."""
-        s = torch.zeros((), dtype=torch.float64, device=stacked.device)
-        out = torch.zeros(stacked.shape[1], dtype=torch.float64,
-                          device=stacked.device)
-        for k in range(stacked.shape[0]):
-            s = s + a[k]
-            out += a[k] * stacked[k]
-        return out * (1.0 / s)
+        # a as a (K, 1) matrix: its row sum is a[0] + a[1] + ... in order
+        return _row_sum(stacked, a) * (1.0 / _row_sum(a.unsqueeze(1)))
 
     def agg_geomed(self, stacked):
         """Smoothed-Weiszfeld geometric median of the updates (module
@@ -464,9 +452,7 @@ class Aggregation:
         last_weights."""
         a = self.geomed_weights(stacked)
         self.last_weights = a / a.sum()
-        if _gpu(stacked):
-            return ext().agg_avg(stacked, a)
-        return self._geomed_mean(stacked, a)
+        return self._mean(stacked, a, self._geomed_mean)
 
     def _log_geomed(self, agent_ids, cur_round):
         if self.writer:
@@ -510,6 +496,16 @@ class Aggregation:
             new = p.double() + lr_vector.double() * agg
         p.copy_(new.float())
 
+    def _buffer_weights(self, agent_ids, device):
+        """What the rule last decided about the agents, read back from
+        last_selected / last_weights; data sizes for the rules that decide
+        nothing about them."""
+        if self.args.aggr == 'krum':
+            return self._krum_weights(len(agent_ids), device)
+        if self.args.aggr == 'geomed':
+            return self.last_weights.to(device)
+        return self._weights(agent_ids, device)
+
     def aggregate_buffers(self, global_model, buffer_deltas, agent_ids):
         """FedAvg-BN: data-weighted mean of BatchNorm running-stat deltas
         (build extension — the reference has no BN).  Under krum: the
@@ -522,12 +518,7 @@ class Aggregation:
             return
         dev = (buffer_deltas.device if isinstance(buffer_deltas, torch.Tensor)
                else buffer_deltas[0].device)
-        if self.args.aggr == 'krum':
-            w = self._krum_weights(len(agent_ids), dev)
-        elif self.args.aggr == 'geomed':
-            w = self.last_weights.to(dev)
-        else:
-            w = self._weights(agent_ids, dev)
+        w = self._buffer_weights(agent_ids, dev)
         if isinstance(buffer_deltas, list):
             buffer_deltas = torch.stack(buffer_deltas)
         if self._server_clip() > 0 and self.last_clip_scale is not None:

@@ -128,18 +128,6 @@ __global__ void apply_update_k(float* __restrict__ params,
   }
 }
 
-__global__ void add_noise_k(double* __restrict__ agg, double std, long n,
-                            uint64_t seed, uint64_t offset) {
-  long stride = (long)gridDim.x * blockDim.x;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += stride) {
-    Philox4 r = philox4(seed, offset, (uint32_t)i);
-    double u1 = (double)u32_to_uniform(r.x);
-    double u2 = (double)u32_to_uniform(r.y);
-    agg[i] += std * sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
-  }
-}
-
 extern "C" {
 void launch_fused_avg_rlr_apply(const double* U, const double* w, int K,
                                 long n, double inv_wsum, int mode_rlr,
@@ -170,10 +158,5 @@ void launch_apply_update(float* params, const double* agg, const double* lr,
                          double slr, long n, void* s) {
   apply_update_k<<<grid_for(n), kBlock, 0, (hipStream_t)s>>>(params, agg, lr,
                                                              slr, n);
-}
-void launch_add_noise(double* agg, double std, long n, uint64_t seed,
-                      uint64_t offset, void* s) {
-  add_noise_k<<<grid_for(n), kBlock, 0, (hipStream_t)s>>>(agg, std, n, seed,
-                                                          offset);
 }
 }

@@ -601,6 +601,30 @@ torch::Tensor delta64(torch::Tensor p, torch::Tensor t0) {
 
 // ------------------------------------------------------------ aggregation
 
+// The two argument checks every server entry point shares.  Each runs
+// before any data_ptr and any launch: a kernel only ever sees pointers
+// whose device, dtype and extent were checked here.
+// A (K, n) update matrix: on device, 2-D, fp64, contiguous,
+// 1 <= K <= max_k, n >= 1.
+static void check_matrix(const torch::Tensor& U, int64_t max_k) {
+  CHK(U.is_cuda());
+  CHK(U.dim() == 2);
+  CHK(U.scalar_type() == torch::kFloat64);
+  CHK(U.is_contiguous());
+  CHK(U.size(0) >= 1 && U.size(0) <= max_k);
+  CHK(U.size(1) >= 1);
+}
+// A vector that belongs to `ref`: on ref's device, 1-D, contiguous, of
+// exactly `len` elements; fp64 like the matrix unless the caller says fp32.
+static void check_vector(const torch::Tensor& v, const torch::Tensor& ref,
+                         int64_t len,
+                         torch::ScalarType dtype = torch::kFloat64) {
+  CHK(v.is_cuda() && v.device() == ref.device());
+  CHK(v.scalar_type() == dtype);
+  CHK(v.dim() == 1 && v.is_contiguous());
+  CHK(v.numel() == len);
+}
+
 // the per-coordinate learning-rate output: n doubles, or empty (and a null
 // pointer to the launcher) when the caller does not want it
 static torch::Tensor lr_buf(bool want_lr, long n, const torch::Tensor& U) {
@@ -612,8 +636,9 @@ torch::Tensor fused_avg_rlr_apply(torch::Tensor U, torch::Tensor w,
                                   double thresh, double slr,
                                   double noise_std, int64_t seed,
                                   int64_t offset, bool want_lr) {
-  CHK_CUDA(U);
-  CHK_CUDA(params);
+  check_matrix(U, INT32_MAX);
+  check_vector(w, U, U.size(0));
+  check_vector(params, U, U.size(1), torch::kFloat32);
   int K = U.size(0);
   long n = U.size(1);
   double wsum = w.sum().item<double>();
@@ -627,7 +652,7 @@ torch::Tensor fused_avg_rlr_apply(torch::Tensor U, torch::Tensor w,
 }
 
 torch::Tensor rlr_vote(torch::Tensor U, double thresh, double slr) {
-  CHK_CUDA(U);
+  check_matrix(U, INT32_MAX);
   int K = U.size(0);
   long n = U.size(1);
   auto lr = torch::empty({n}, U.options());
@@ -637,7 +662,8 @@ torch::Tensor rlr_vote(torch::Tensor U, double thresh, double slr) {
 }
 
 torch::Tensor agg_avg(torch::Tensor U, torch::Tensor w) {
-  CHK_CUDA(U);
+  check_matrix(U, INT32_MAX);
+  check_vector(w, U, U.size(0));
   int K = U.size(0);
   long n = U.size(1);
   double wsum = w.sum().item<double>();
@@ -648,7 +674,7 @@ torch::Tensor agg_avg(torch::Tensor U, torch::Tensor w) {
 }
 
 torch::Tensor agg_sign(torch::Tensor U) {
-  CHK_CUDA(U);
+  check_matrix(U, INT32_MAX);
   auto out = torch::empty({U.size(1)}, U.options());
   launch_agg_sign(U.data_ptr<double>(), U.size(0), U.size(1),
                   out.data_ptr<double>(), stream_of(U));
@@ -656,30 +682,18 @@ torch::Tensor agg_sign(torch::Tensor U) {
 }
 
 torch::Tensor agg_comed(torch::Tensor U) {
-  CHK_CUDA(U);
-  CHK(U.size(0) <= 64);
+  check_matrix(U, 64);
   auto out = torch::empty({U.size(1)}, U.options());
   launch_agg_comed(U.data_ptr<double>(), U.size(0), U.size(1),
                    out.data_ptr<double>(), stream_of(U));
   return out;
 }
 
-// Shared argument checks of the order-statistic entry points: (K, n) fp64,
-// contiguous, on device, 1 <= K <= orderstat_max_k(), 0 <= lo < hi <= K.
-static void check_orderstat(const torch::Tensor& U, int64_t lo, int64_t hi) {
-  CHK(U.is_cuda());
-  CHK(U.dim() == 2);
-  CHK(U.scalar_type() == torch::kFloat64);
-  CHK(U.is_contiguous());
-  CHK(U.size(0) >= 1 && U.size(0) <= orderstat_max_k());
-  CHK(U.size(1) >= 1);
-  CHK(0 <= lo && lo < hi && hi <= U.size(0));
-}
-
 std::tuple<torch::Tensor, torch::Tensor> agg_orderstat(
     torch::Tensor U, int64_t lo, int64_t hi, bool want_lr, double thresh,
     double slr) {
-  check_orderstat(U, lo, hi);
+  check_matrix(U, orderstat_max_k());
+  CHK(0 <= lo && lo < hi && hi <= U.size(0));
   int K = U.size(0);
   long n = U.size(1);
   auto out = torch::empty({n}, U.options());
@@ -694,11 +708,9 @@ std::tuple<torch::Tensor, torch::Tensor> agg_orderstat(
 torch::Tensor orderstat_rlr_apply(torch::Tensor U, int64_t lo, int64_t hi,
                                   torch::Tensor params, bool rlr,
                                   double thresh, double slr, bool want_lr) {
-  check_orderstat(U, lo, hi);
-  CHK(params.is_cuda() && params.is_contiguous());
-  CHK(params.device() == U.device());
-  CHK(params.scalar_type() == torch::kFloat32);
-  CHK(params.numel() == U.size(1));
+  check_matrix(U, orderstat_max_k());
+  CHK(0 <= lo && lo < hi && hi <= U.size(0));
+  check_vector(params, U, U.size(1), torch::kFloat32);
   int K = U.size(0);
   long n = U.size(1);
   auto lr = lr_buf(want_lr, n, U);
@@ -710,18 +722,8 @@ torch::Tensor orderstat_rlr_apply(torch::Tensor U, int64_t lo, int64_t hi,
   return lr;
 }
 
-// (K, n) fp64, contiguous, on device, 1 <= K <= pairdist_max_k(), n >= 1.
-static void check_pairdist(const torch::Tensor& U) {
-  CHK(U.is_cuda());
-  CHK(U.dim() == 2);
-  CHK(U.scalar_type() == torch::kFloat64);
-  CHK(U.is_contiguous());
-  CHK(U.size(0) >= 1 && U.size(0) <= pairdist_max_k());
-  CHK(U.size(1) >= 1);
-}
-
 torch::Tensor pairwise_sqdist(torch::Tensor U) {
-  check_pairdist(U);
+  check_matrix(U, pairdist_max_k());
   int K = U.size(0);
   long n = U.size(1);
   auto ws = torch::empty({pairdist_ws_doubles(K, n)}, U.options());
@@ -731,23 +733,10 @@ torch::Tensor pairwise_sqdist(torch::Tensor U) {
   return D;
 }
 
-// (K, n) fp64, contiguous, on device, 1 <= K <= geomed_max_k(), n >= 1.
-static void check_geomed(const torch::Tensor& U) {
-  CHK(U.is_cuda());
-  CHK(U.dim() == 2);
-  CHK(U.scalar_type() == torch::kFloat64);
-  CHK(U.is_contiguous());
-  CHK(U.size(0) >= 1 && U.size(0) <= geomed_max_k());
-  CHK(U.size(1) >= 1);
-}
-
 // d2[k] = ||U_k - z||^2, z the weighted mean of the rows under a (K fp64)
 torch::Tensor geomed_sqdist(torch::Tensor U, torch::Tensor a) {
-  check_geomed(U);
-  CHK(a.is_cuda() && a.device() == U.device());
-  CHK(a.dim() == 1 && a.numel() == U.size(0));
-  CHK(a.scalar_type() == torch::kFloat64);
-  CHK(a.is_contiguous());
+  check_matrix(U, geomed_max_k());
+  check_vector(a, U, U.size(0));
   int K = U.size(0);
   long n = U.size(1);
   auto ws = torch::empty({geomed_ws_doubles(K, n)}, U.options());
@@ -762,7 +751,7 @@ torch::Tensor geomed_sqdist(torch::Tensor U, torch::Tensor a) {
 std::tuple<torch::Tensor, torch::Tensor> geomed_weights(torch::Tensor U,
                                                         int64_t iters,
                                                         double nu) {
-  check_geomed(U);
+  check_matrix(U, geomed_max_k());
   CHK(iters >= 0);
   CHK(nu > 0.0);
   int K = U.size(0);
@@ -774,16 +763,6 @@ std::tuple<torch::Tensor, torch::Tensor> geomed_weights(torch::Tensor U,
                         ws.data_ptr<double>(), a.data_ptr<double>(),
                         d2.data_ptr<double>(), stream_of(U));
   return {a, d2};
-}
-
-// (K, n) fp64, contiguous, on device, K >= 1, n >= 1: no upper limit on K.
-static void check_rowclip(const torch::Tensor& U) {
-  CHK(U.is_cuda());
-  CHK(U.dim() == 2);
-  CHK(U.scalar_type() == torch::kFloat64);
-  CHK(U.is_contiguous());
-  CHK(U.size(0) >= 1 && U.size(0) <= INT32_MAX);
-  CHK(U.size(1) >= 1);
 }
 
 // the caller's workspace (at least rownorm_ws_doubles(K, n) doubles), or a
@@ -800,9 +779,10 @@ static torch::Tensor rowclip_ws(const torch::Tensor& U,
   return w;
 }
 
-// stage 1 alone: the (chunks, K) partial sums of squares
+// stage 1 alone: the (chunks, K) partial sums of squares.  The row-norm
+// entry points put no limit of their own on K.
 torch::Tensor rownorm_partials(torch::Tensor U) {
-  check_rowclip(U);
+  check_matrix(U, INT32_MAX);
   int K = U.size(0);
   long n = U.size(1);
   auto ws = torch::empty({(long)rownorm_chunks(K, n), (long)K}, U.options());
@@ -813,7 +793,7 @@ torch::Tensor rownorm_partials(torch::Tensor U) {
 
 // norm[k] = ||U_k||_2
 torch::Tensor row_norms(torch::Tensor U, c10::optional<torch::Tensor> ws) {
-  check_rowclip(U);
+  check_matrix(U, INT32_MAX);
   int K = U.size(0);
   long n = U.size(1);
   auto w = rowclip_ws(U, ws);
@@ -828,7 +808,7 @@ torch::Tensor row_norms(torch::Tensor U, c10::optional<torch::Tensor> ws) {
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> rowclip_(
     torch::Tensor U, double value, bool median_mode,
     c10::optional<torch::Tensor> ws) {
-  check_rowclip(U);
+  check_matrix(U, INT32_MAX);
   CHK(value >= 0.0);
   int K = U.size(0);
   long n = U.size(1);
@@ -843,18 +823,16 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> rowclip_(
   return {scale, norm, tau};
 }
 
+// lr is the per-coordinate rate, or empty (of any dtype) for the constant slr
 void apply_update(torch::Tensor params, torch::Tensor agg, torch::Tensor lr,
                   double slr) {
-  CHK_CUDA(params);
+  CHK(params.is_cuda());
+  check_vector(params, params, params.numel(), torch::kFloat32);
+  check_vector(agg, params, params.numel());
+  if (lr.numel()) check_vector(lr, params, params.numel());
   launch_apply_update(params.data_ptr<float>(), agg.data_ptr<double>(),
                       lr.numel() ? lr.data_ptr<double>() : nullptr, slr,
                       params.numel(), stream_of(params));
-}
-
-void add_noise(torch::Tensor agg, double std, int64_t seed, int64_t offset) {
-  CHK_CUDA(agg);
-  launch_add_noise(agg.data_ptr<double>(), std, agg.numel(), (uint64_t)seed,
-                   (uint64_t)offset, stream_of(agg));
 }
 
 // ------------------------------------------------------------ gemm/linear
@@ -1613,7 +1591,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("median_mode"), py::arg("ws") = py::none());
   m.def("rownorm_chunks", &rownorm_chunks);
   m.def("rownorm_ws_doubles", &rownorm_ws_doubles);
-  m.def("add_noise", &add_noise);
   m.def("gemm", &gemm);
   m.def("gemm_bf16", &gemm_bf16);
   m.def("nhwc_flatten", &nhwc_flatten);

@@ -228,8 +228,6 @@ void launch_agg_sign(const double* U, int K, long n, double* out, void* s);
 void launch_agg_comed(const double* U, int K, long n, double* out, void* s);
 void launch_apply_update(float* params, const double* agg, const double* lr,
                          double slr, long n, void* s);
-void launch_add_noise(double* agg, double std, long n, uint64_t seed,
-                      uint64_t offset, void* s);
 // orderstat.hip (lr_out is nullable)
 int orderstat_max_k();
 void launch_agg_orderstat(const double* U, int K, long n, int lo, int hi,

@@ -135,6 +135,25 @@ def args_parser(argv=None):
         parser.error(str(e))
 
 
+def check_geomed(iters, nu):
+    """The K-independent limits of --aggr geomed, for the parser and for a
+    server that is handed its args directly."""
+    if iters < 0:
+        raise ValueError(f"--geomed_iters must be >= 0, got {iters}")
+    if not nu > 0:
+        raise ValueError(f"--geomed_nu must be > 0, got {nu}")
+
+
+def check_server_clip(value, mode):
+    """Likewise for the server-side norm clip."""
+    if not value >= 0:
+        raise ValueError(f"--server_clip must be >= 0, got {value}")
+    if mode not in SERVER_CLIP_MODES:
+        raise ValueError(
+            f"--server_clip_mode must be one of {SERVER_CLIP_MODES}, got "
+            f"{mode}")
+
+
 def finalize_args(args):
     """Derived rules. server_lr forced to 1 unless aggr=='sign'
     (reference federated.py:23); 0 <= trim_frac < 0.5 so that at least one
@@ -150,18 +169,8 @@ def finalize_args(args):
         raise ValueError(
             f"--krum_f and --krum_m must be >= 0, got {args.krum_f} and "
             f"{args.krum_m}")
-    if args.geomed_iters < 0:
-        raise ValueError(
-            f"--geomed_iters must be >= 0, got {args.geomed_iters}")
-    if not args.geomed_nu > 0:
-        raise ValueError(f"--geomed_nu must be > 0, got {args.geomed_nu}")
-    if not args.server_clip >= 0:
-        raise ValueError(
-            f"--server_clip must be >= 0, got {args.server_clip}")
-    if args.server_clip_mode not in SERVER_CLIP_MODES:
-        raise ValueError(
-            f"--server_clip_mode must be one of {SERVER_CLIP_MODES}, got "
-            f"{args.server_clip_mode}")
+    check_geomed(args.geomed_iters, args.geomed_nu)
+    check_server_clip(args.server_clip, args.server_clip_mode)
     if not 0 < args.attack_boost < float('inf'):
         raise ValueError(
             f"--attack_boost must be > 0, got {args.attack_boost}")

@@ -1,22 +1,20 @@
 """Unit tests for the aggregation rules against tiny closed-form cases
 (reference semantics: src/aggregation.py:48-75)."""
 
+import functools
+
 import pytest
 import torch
 
-from rlr_amd.aggregation import Aggregation
-from rlr_amd.options import default_args
+import server_helpers
 
 
-def make_agg(**over):
-    args = default_args(no_tb=True, **over)
-    sizes = {i: 10 * (i + 1) for i in range(8)}
-    return Aggregation(sizes, 6, None, args), args
+make_agg = functools.partial(server_helpers.make_agg, 6, table=8)
 
 
 def test_rlr_vote_hand_built():
     # theta=3, 4 agents; per-coordinate |sum of signs|
-    agg, _ = make_agg(robustLR_threshold=3, aggr='avg')
+    agg = make_agg(robustLR_threshold=3, aggr='avg')
     U = torch.tensor([
         [+1.0, -2.0, +0.5, 0.0, +1.0, -1.0],
         [+2.0, -1.0, -0.5, 0.0, +1.0, -1.0],
@@ -30,7 +28,7 @@ def test_rlr_vote_hand_built():
 
 
 def test_rlr_vote_threshold_boundary():
-    agg, _ = make_agg(robustLR_threshold=2, aggr='avg')
+    agg = make_agg(robustLR_threshold=2, aggr='avg')
     U = torch.tensor([[+1.0, +1.0], [+1.0, -1.0]], dtype=torch.float64)
     lr = agg.compute_robustLR(U)
     # sums: 2 (== theta -> +), 0 (< theta -> -)
@@ -38,7 +36,7 @@ def test_rlr_vote_threshold_boundary():
 
 
 def test_fedavg_weighting():
-    agg, _ = make_agg(aggr='avg')
+    agg = make_agg(aggr='avg')
     U = torch.tensor([[1.0] * 6, [4.0] * 6], dtype=torch.float64)
     out = agg.agg_avg(U, [0, 1])  # sizes 10, 20
     expect = (10 * 1.0 + 20 * 4.0) / 30
@@ -47,14 +45,14 @@ def test_fedavg_weighting():
 
 @pytest.mark.parametrize("k", [3, 4, 5, 8])
 def test_comed_matches_torch_median(k):
-    agg, _ = make_agg(aggr='comed')
+    agg = make_agg(aggr='comed')
     U = torch.randn(k, 101, dtype=torch.float64)
     out = agg.agg_comed(U)
     assert torch.equal(out, torch.median(U, dim=0).values)
 
 
 def test_sign_aggregate():
-    agg, _ = make_agg(aggr='sign')
+    agg = make_agg(aggr='sign')
     U = torch.tensor([[+5.0, -1.0, 0.0], [+1.0, -2.0, 0.0],
                       [-9.0, +7.0, 0.0]], dtype=torch.float64)
     out = agg.agg_sign(U)
@@ -64,7 +62,7 @@ def test_sign_aggregate():
 def test_apply_update_fp64_to_fp32():
     """theta <- float32(theta + lr*agg) (reference aggregation.py:38-40)."""
     from rlr_amd.flatmodel import FlatParamModel
-    agg, args = make_agg(aggr='avg')
+    agg = make_agg(aggr='avg')
 
     class M(torch.nn.Module):
         def __init__(self):
@@ -82,7 +80,7 @@ def test_apply_update_fp64_to_fp32():
 def test_rlr_applied_sign_flip():
     """End-to-end: coords below threshold move AGAINST the aggregate."""
     from rlr_amd.flatmodel import FlatParamModel
-    agg, args = make_agg(aggr='avg', robustLR_threshold=2)
+    agg = make_agg(aggr='avg', robustLR_threshold=2)
 
     class M(torch.nn.Module):
         def __init__(self):
@@ -100,7 +98,7 @@ def test_rlr_applied_sign_flip():
 
 
 def test_noise_deterministic_per_round():
-    agg, _ = make_agg(aggr='avg', noise=0.5, clip=2.0)
+    agg = make_agg(aggr='avg', noise=0.5, clip=2.0)
     n1 = agg._noise(3, torch.device('cpu'), torch.float64)
     n2 = agg._noise(3, torch.device('cpu'), torch.float64)
     n3 = agg._noise(4, torch.device('cpu'), torch.float64)
@@ -112,7 +110,7 @@ def test_noise_deterministic_per_round():
 def test_dict_api_parity():
     """The reference dict-based call path still works."""
     from rlr_amd.flatmodel import FlatParamModel
-    agg, _ = make_agg(aggr='avg')
+    agg = make_agg(aggr='avg')
 
     class M(torch.nn.Module):
         def __init__(self):

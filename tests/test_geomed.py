@@ -5,43 +5,26 @@ CPU path, and the kernel's workspace arithmetic (host only)."""
 
 import functools
 import math
-import os
 from time import ctime
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 from rlr_amd.aggregation import Aggregation
 from rlr_amd.options import args_parser, default_args
 from rlr_amd.utils.logging import print_exp_details, run_name
 
-N = 4099
+import server_helpers
+from server_helpers import N, P as _P, Writer, clustered, t64
+
 NU = 1e-6
 KF = [(4, 1), (10, 2), (65, 10), (338, 33), (512, 100)]
 
 
-def make_agg(n=2, **over):
-    args = default_args(no_tb=True, aggr='geomed', device='cpu', **over)
-    sizes = {i: 10 * (i + 1) for i in range(1024)}
-    return Aggregation(sizes, n, None, args), args
-
-
-def t64(rows):
-    return torch.tensor(rows, dtype=torch.float64)
-
-
-@functools.lru_cache(maxsize=None)
-def clustered(K, f, n=N):
-    """Honest rows base + 0.3 randn; f random rows -2 base + 0.3 randn.
-    Returns (U, sorted positions of the corrupted rows)."""
-    g = torch.Generator().manual_seed(31 * K + f)
-    base = torch.randn(n, dtype=torch.float64, generator=g)
-    U = base + 0.3 * torch.randn(K, n, dtype=torch.float64, generator=g)
-    bad = torch.randperm(K, generator=g)[:f].sort().values
-    U[bad] = -2.0 * base + 0.3 * torch.randn(f, n, dtype=torch.float64,
-                                             generator=g)
-    return U, bad
+make_agg = functools.partial(server_helpers.make_agg, n=2, dev='cpu',
+                             aggr='geomed')
+_run_world = functools.partial(server_helpers.run_world, base_port=29591,
+                               aggr='geomed', geomed_iters=3)
 
 
 # ------------------------------------------------------------ closed form
@@ -50,7 +33,7 @@ def clustered(K, f, n=N):
 # nu * sum_{k != p} a_k |x_k - p| <= nu * (K - 1) of p.  10 nu covers that.
 
 def test_collinear_points_give_the_middle_point():
-    agg, _ = make_agg(geomed_iters=32, geomed_nu=NU)
+    agg = make_agg(geomed_iters=32, geomed_nu=NU)
     U = t64([[0, 0], [1, 0], [10, 0]])
     z = agg.agg_geomed(U)
     assert (z - t64([1, 0])).norm() <= 10 * NU, z
@@ -62,14 +45,14 @@ def test_collinear_points_give_the_middle_point():
 def test_four_points_with_a_data_point_median():
     # unit vectors from (1,1) to the others sum to (-0.205, -0.129):
     # norm 0.24 < 1, so (1,1) is the geometric median
-    agg, _ = make_agg(geomed_iters=48, geomed_nu=NU)
+    agg = make_agg(geomed_iters=48, geomed_nu=NU)
     U = t64([[0, 0], [4, 0], [0, 3], [1, 1]])
     z = agg.agg_geomed(U)
     assert (z - t64([1, 1])).norm() <= 10 * NU, z
 
 
 def test_equilateral_triangle_gives_the_centroid():
-    agg, _ = make_agg()
+    agg = make_agg()
     U = t64([[0, 0], [1, 0], [0.5, math.sqrt(3) / 2]])
     z = agg.agg_geomed(U)
     assert torch.allclose(z, U.sum(0) / 3, rtol=0, atol=1e-14)
@@ -78,7 +61,7 @@ def test_equilateral_triangle_gives_the_centroid():
 
 def test_zero_iterations_is_the_unweighted_mean_bitwise():
     U, _ = clustered(10, 2)
-    agg, _ = make_agg(n=N, geomed_iters=0)
+    agg = make_agg(n=N, geomed_iters=0)
     out = torch.zeros(N, dtype=torch.float64)
     for k in range(10):
         out += U[k]
@@ -92,11 +75,11 @@ def test_zero_iterations_is_the_unweighted_mean_bitwise():
 def test_weights_are_the_rule_as_written():
     """One and two iterations by hand."""
     U = t64([[0, 0], [4, 0], [0, 3], [1, 1], [7, 7]])
-    agg, _ = make_agg(geomed_iters=1)
+    agg = make_agg(geomed_iters=1)
     z0 = U.sum(0) / 5
     a1 = 1.0 / (U - z0).norm(dim=1)
     assert torch.allclose(agg.geomed_weights(U), a1, rtol=1e-14)
-    agg, _ = make_agg(geomed_iters=2)
+    agg = make_agg(geomed_iters=2)
     z1 = (a1.unsqueeze(1) * U).sum(0) / a1.sum()
     a2 = 1.0 / (U - z1).norm(dim=1)
     assert torch.allclose(agg.geomed_weights(U), a2, rtol=1e-14)
@@ -106,7 +89,7 @@ def test_weights_are_the_rule_as_written():
 
 def test_nu_caps_the_weight_of_a_row_at_the_mean():
     # the mean of these rows is row 1 itself: distance 0, weight 1 / nu
-    agg, _ = make_agg(geomed_iters=1, geomed_nu=0.25)
+    agg = make_agg(geomed_iters=1, geomed_nu=0.25)
     a = agg.geomed_weights(t64([[-1, 0], [0, 0], [1, 0]]))
     assert a.tolist() == [1.0, 4.0, 1.0]
 
@@ -120,7 +103,7 @@ def test_breakdown_one_outlier_of_five():
     1e6 * 0.2 / 4^8 ~ 3).  Both medians then lie by the honest square, so
     they are within its diameter of each other."""
     honest = t64([[0, 0], [1, 0], [0, 1], [1, 1]])
-    agg, _ = make_agg(geomed_iters=32)
+    agg = make_agg(geomed_iters=32)
     far = {}
     mean = {}
     for scale in (10.0, 1e6):
@@ -144,12 +127,12 @@ def test_objective_is_non_increasing():
     U, _ = clustered(10, 2)
     prev = None
     for R in range(0, 9):
-        agg, _ = make_agg(n=N, geomed_iters=R)
+        agg = make_agg(n=N, geomed_iters=R)
         obj = objective(U, agg.agg_geomed(U))
         if prev is not None:
             assert obj <= prev * (1 + 1e-12), (R, obj, prev)
         prev = obj
-    agg, _ = make_agg(n=N, geomed_iters=0)
+    agg = make_agg(n=N, geomed_iters=0)
     assert prev < objective(U, agg.agg_geomed(U)) * 0.999
 
 
@@ -158,7 +141,7 @@ def test_objective_is_non_increasing():
 @pytest.mark.parametrize("K,f", KF)
 def test_corrupted_rows_weigh_less_than_every_honest_row(K, f):
     U, bad = clustered(K, f)
-    agg, _ = make_agg(n=N)
+    agg = make_agg(n=N)
     agg.agg_geomed(U)
     w = agg.last_weights
     good = torch.ones(K, dtype=torch.bool)
@@ -234,12 +217,6 @@ def test_banner_line_only_for_geomed(capsys):
 
 # ------------------------------------------------------------ server level
 
-class _P(torch.nn.Module):
-    def __init__(self, n):
-        super().__init__()
-        self.p = torch.nn.Parameter(torch.zeros(n))
-
-
 # K = 5; agent 4 is the outlier.  coord 0: all five positive, |vote| = 5.
 # coord 1: signs + + - - (+ from the outlier): |vote| = 1.
 U_VOTE = t64([[1, 1], [1, 2], [1, -1], [1, -4], [100, 100]])
@@ -251,11 +228,11 @@ def test_rlr_with_geomed_sign_flip():
     AGAINST the aggregate."""
     from rlr_amd.flatmodel import FlatParamModel
     ids = [0, 1, 2, 3, 4]
-    ref, _ = make_agg()
+    ref = make_agg()
     z = ref.agg_geomed(U_VOTE)
     assert z[0] > 0 and z[1] != 0
     for theta, sign in ((0, (1, 1)), (4, (1, -1)), (5, (1, -1))):
-        agg, _ = make_agg(robustLR_threshold=theta)
+        agg = make_agg(robustLR_threshold=theta)
         gm = FlatParamModel(_P(2), 'cpu')
         agg.aggregate_updates(gm, U_VOTE, cur_round=1, agent_ids=ids)
         want = (t64(sign) * z).float()
@@ -266,17 +243,10 @@ def test_rlr_with_geomed_sign_flip():
 
 
 def test_corrupt_weight_is_logged():
-    class W:
-        def __init__(self):
-            self.rows = []
-
-        def add_scalar(self, name, v, step):
-            self.rows.append((name, v, step))
-
     from rlr_amd.flatmodel import FlatParamModel
     args = default_args(no_tb=True, aggr='geomed', device='cpu',
                         num_corrupt=2)
-    w = W()
+    w = Writer()
     agg = Aggregation({i: 1 for i in range(8)}, 2, None, args, writer=w)
     gm = FlatParamModel(_P(2), 'cpu')
     order = [4, 1, 3, 0, 2]
@@ -298,7 +268,7 @@ def test_buffers_are_averaged_with_last_weights():
             self.p = torch.nn.Parameter(torch.zeros(2))
             self.register_buffer('b', torch.zeros(3))
 
-    agg, _ = make_agg()
+    agg = make_agg()
     gm = FlatParamModel(BN(), 'cpu')
     ids = [0, 1, 2, 3, 4]
     agg.aggregate_updates(gm, U_VOTE, cur_round=1, agent_ids=ids)
@@ -328,42 +298,6 @@ def test_driver_runs_geomed(tiny_args, tiny_sizes):
     assert torch.isfinite(h['final_params']).all()
     assert h['final_params'].shape == initial.shape
     assert not torch.equal(h['final_params'], initial)
-
-
-def _worker(rank, world_size, port, out_q):
-    os.environ['RANK'] = str(rank)
-    os.environ['WORLD_SIZE'] = str(world_size)
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    import rlr_amd.data.datasets as D
-    D.DEFAULT_SIZES['fmnist'] = (2000, 400)
-    from rlr_amd.federated import run
-    from rlr_amd.parallel import dist as pdist
-    args = default_args(num_agents=4, rounds=2, snap=2, local_ep=1, bs=64,
-                        synthetic=True, no_tb=True, data='fmnist',
-                        num_corrupt=1, poison_frac=0.5, aggr='geomed',
-                        geomed_iters=3, robustLR_threshold=3, device='cpu')
-    try:
-        h = run(args)
-        if rank == 0:
-            out_q.put(h['final_params'].numpy().copy())
-    finally:
-        pdist.teardown()
-
-
-def _run_world(world_size):
-    ctx = mp.get_context('spawn')
-    q = ctx.Queue()
-    port = 29591 + world_size
-    procs = [ctx.Process(target=_worker, args=(r, world_size, port, q))
-             for r in range(world_size)]
-    for p in procs:
-        p.start()
-    params = q.get(timeout=300)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    return torch.from_numpy(params)
 
 
 @pytest.mark.timeout(900)

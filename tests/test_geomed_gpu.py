@@ -10,6 +10,9 @@ import functools
 import pytest
 import torch
 
+import server_helpers
+from server_helpers import P as _P, clustered, randn
+
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
@@ -32,12 +35,7 @@ def ext():
     return _e()
 
 
-def make_agg(n, dev, **over):
-    from rlr_amd.aggregation import Aggregation
-    from rlr_amd.options import default_args
-    args = default_args(no_tb=True, device=dev, aggr='geomed', **over)
-    sizes = {i: 10 * (i + 1) for i in range(1024)}
-    return Aggregation(sizes, n, None, args)
+make_agg = functools.partial(server_helpers.make_agg, aggr='geomed')
 
 
 # ------------------------------------------------------------------ inputs
@@ -47,25 +45,6 @@ def make_agg(n, dev, **over):
 def ints(K, n=N):
     g = torch.Generator().manual_seed(7 * K + n)
     return torch.randint(-3, 4, (K, n), generator=g).double()
-
-
-@functools.lru_cache(maxsize=None)
-def randn(K, n=N):
-    g = torch.Generator().manual_seed(1000 * K + n)
-    return torch.randn(K, n, dtype=torch.float64, generator=g)
-
-
-@functools.lru_cache(maxsize=None)
-def clustered(K, f, n=N):
-    """Honest rows base + 0.3 randn; f random rows -2 base + 0.3 randn.
-    Returns (U, sorted positions of the corrupted rows)."""
-    g = torch.Generator().manual_seed(31 * K + f)
-    base = torch.randn(n, dtype=torch.float64, generator=g)
-    U = base + 0.3 * torch.randn(K, n, dtype=torch.float64, generator=g)
-    bad = torch.randperm(K, generator=g)[:f].sort().values
-    U[bad] = -2.0 * base + 0.3 * torch.randn(f, n, dtype=torch.float64,
-                                             generator=g)
-    return U, bad
 
 
 def cpu_sqdist(U, a):
@@ -244,12 +223,6 @@ def test_end_to_end_against_the_cpu_rule(K, f):
           f"weights = {rel(w, w_ref):.3e}")
     assert rel(z, z_ref) <= E2E_BOUND
     assert rel(w, w_ref) <= E2E_BOUND
-
-
-class _P(torch.nn.Module):
-    def __init__(self, n):
-        super().__init__()
-        self.p = torch.nn.Parameter(torch.zeros(n))
 
 
 @pytest.mark.parametrize("K,f,theta", [(10, 2, 4), (65, 10, 0)])

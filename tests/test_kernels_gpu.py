@@ -199,14 +199,108 @@ def test_fused_avg_rlr_apply_matches_pieces(ext):
     t_allclose(p_fused, p, rtol=1e-6, atol=1e-7, msg='fused vs pieces')
 
 
-def test_add_noise_deterministic(ext):
-    a = torch.zeros(1 << 16, dtype=torch.float64, device=DEV)
-    b = torch.zeros(1 << 16, dtype=torch.float64, device=DEV)
-    ext.add_noise(a, 0.5, 99, 3)
-    ext.add_noise(b, 0.5, 99, 3)
-    assert torch.equal(a, b)
-    assert abs(a.mean().item()) < 0.02
-    assert abs(a.std().item() - 0.5) < 0.02
+# Argument checks of the server entry points.  Every rejected call must
+# return before a launch and before a data_ptr: these tests rely on nothing
+# reaching the device, they do not probe what a kernel does with a bad
+# pointer.
+CK, CN = 4, 33
+
+
+def _check_inputs():
+    g = torch.Generator().manual_seed(11)
+    U = torch.randn(CK, CN, dtype=torch.float64, generator=g).to(DEV)
+    w = (torch.arange(CK, device=DEV) + 1).double()
+    p = torch.randn(CN, generator=g).to(DEV)
+    return U, w, p
+
+
+def _bad_U(U):
+    return [U.float(),                                     # fp32
+            torch.zeros(CN, CK, dtype=torch.float64, device=DEV).T,
+            U[0],                                          # 1-d
+            U.cpu()]
+
+
+def _bad_w(w):
+    w2 = torch.ones(2 * CK, dtype=torch.float64, device=DEV)
+    assert w2[::2].numel() == CK and not w2[::2].is_contiguous()
+    return [w.cpu(), w.float(), w[:CK - 1], w2[::2]]
+
+
+def _rejects(fn, *args):
+    with pytest.raises(RuntimeError):
+        fn(*args)
+
+
+def test_fused_avg_rlr_apply_argument_checks(ext):
+    U, w, p = _check_inputs()
+    tail = (True, 3.0, 1.0, 0.0, 0, 0, False)
+    for X in _bad_U(U):
+        _rejects(ext.fused_avg_rlr_apply, X, w, p, *tail)
+    for x in _bad_w(w):
+        _rejects(ext.fused_avg_rlr_apply, U, x, p, *tail)
+    for q in (p.double(), p[:CN - 1]):
+        _rejects(ext.fused_avg_rlr_apply, U, w, q, *tail)
+    ref = p.clone()
+    ext.apply_update(ref, ext.agg_avg(U, w), ext.rlr_vote(U, 3.0, 1.0), 1.0)
+    ext.fused_avg_rlr_apply(U, w, p, *tail)
+    t_allclose(p, ref, rtol=1e-6, atol=1e-7, msg='fused vs pieces')
+
+
+def test_agg_avg_argument_checks(ext):
+    U, w, _ = _check_inputs()
+    for X in _bad_U(U):
+        _rejects(ext.agg_avg, X, w)
+    for x in _bad_w(w):
+        _rejects(ext.agg_avg, U, x)
+    ref = (U * w[:, None]).sum(0) / w.sum()
+    t_allclose(ext.agg_avg(U, w), ref, rtol=1e-12, atol=1e-12, msg='avg')
+
+
+def test_rlr_vote_argument_checks(ext):
+    U, _, _ = _check_inputs()
+    for X in _bad_U(U):
+        _rejects(ext.rlr_vote, X, 2.0, 1.0)
+    ref = torch.where(torch.sign(U).sum(0).abs() >= 2, 1.0, -1.0).double()
+    assert torch.equal(ext.rlr_vote(U, 2.0, 1.0), ref)
+
+
+def test_agg_sign_argument_checks(ext):
+    U, _, _ = _check_inputs()
+    for X in _bad_U(U):
+        _rejects(ext.agg_sign, X)
+    assert torch.equal(ext.agg_sign(U), torch.sign(torch.sign(U).sum(0)))
+
+
+def test_agg_comed_argument_checks(ext):
+    U, _, _ = _check_inputs()
+    for X in _bad_U(U):
+        _rejects(ext.agg_comed, X)
+    _rejects(ext.agg_comed,
+             torch.zeros(65, CN, dtype=torch.float64, device=DEV))
+    assert torch.equal(ext.agg_comed(U), torch.median(U, dim=0).values)
+
+
+def test_apply_update_argument_checks(ext):
+    U, w, p = _check_inputs()
+    agg = U[0].clone()
+    lr = torch.where(U[1] > 0, 1.0, -1.0).double()
+    none = torch.empty(0, device=DEV)
+    for q in (p.double(), p[:CN - 1], p.cpu()):
+        _rejects(ext.apply_update, q, agg, lr, 1.0)
+    for a in (agg.float(), agg[:CN - 1], agg.cpu()):
+        _rejects(ext.apply_update, p, a, lr, 1.0)
+        _rejects(ext.apply_update, p, a, none, 1.0)
+    for x in (lr[:CN - 1], lr.float(), lr.cpu()):
+        _rejects(ext.apply_update, p, agg, x, 1.0)
+    ref = (p.double() + lr * agg).float()
+    ref_const = (p.double() + 0.5 * agg).float()
+    p_const = p.clone()
+    ext.apply_update(p, agg, lr, 1.0)
+    assert torch.equal(p, ref)
+    # no per-coordinate rate: an empty tensor, of any dtype
+    ext.apply_update(p_const, agg, none, 0.5)
+    assert torch.equal(p_const, ref_const)
 
 
 # ------------------------------------------------------------ gemm/linear

@@ -2,26 +2,24 @@
 CLI surface, the RLR vote on top, the driver and world-size invariance on
 the CPU path, and the kernel's workspace arithmetic (host only)."""
 
-import os
+import functools
 from time import ctime
 
 import pytest
 import torch
-import torch.multiprocessing as mp
 
 from rlr_amd.aggregation import Aggregation
 from rlr_amd.options import args_parser, default_args
 from rlr_amd.utils.logging import print_exp_details, run_name
 
-
-def make_agg(n=2, **over):
-    args = default_args(no_tb=True, aggr='krum', device='cpu', **over)
-    sizes = {i: 10 * (i + 1) for i in range(32)}
-    return Aggregation(sizes, n, None, args), args
+import server_helpers
+from server_helpers import P as _P, Writer, t64
 
 
-def t64(rows):
-    return torch.tensor(rows, dtype=torch.float64)
+make_agg = functools.partial(server_helpers.make_agg, n=2, dev='cpu',
+                             aggr='krum', table=32)
+_run_world = functools.partial(server_helpers.run_world, base_port=29561,
+                               aggr='krum', krum_f=1)
 
 
 # four honest agents near the origin and one far outlier; every distance is
@@ -46,14 +44,14 @@ S5 = t64([(1 + 1) * 0.5, (1 + 1) * 0.5, (1 + 2) * 0.5, (1 + 4) * 0.5,
 # ------------------------------------------------------------ closed form
 
 def test_closed_form_distances_and_scores():
-    agg, _ = make_agg(krum_f=1)
+    agg = make_agg(krum_f=1)
     D = agg.pairwise_sqdist(U5)
     assert torch.equal(D, D5)
     assert torch.equal(agg.krum_scores(D), S5)
 
 
 def test_closed_form_classic_krum_m1():
-    agg, _ = make_agg(krum_f=1, krum_m=1)
+    agg = make_agg(krum_f=1, krum_m=1)
     # agents 0 and 1 tie at score 1.0: the lower position wins
     assert agg.krum_select(U5).tolist() == [0]
     assert torch.equal(agg.agg_krum(U5), U5[0])
@@ -61,7 +59,7 @@ def test_closed_form_classic_krum_m1():
 
 
 def test_closed_form_multi_krum_m0():
-    agg, _ = make_agg(krum_f=1, krum_m=0)         # m = K - f = 4
+    agg = make_agg(krum_f=1, krum_m=0)         # m = K - f = 4
     sel = agg.krum_select(U5)
     assert sel.dtype == torch.long and sel.tolist() == [0, 1, 2, 3]
     expect = t64([(0 + 1 + 0 + 2) * 0.25, (0 + 0 + 1 + 0) * 0.25])
@@ -69,7 +67,7 @@ def test_closed_form_multi_krum_m0():
 
 
 def test_selection_is_returned_in_sampled_order():
-    agg, _ = make_agg(krum_f=1, krum_m=3)
+    agg = make_agg(krum_f=1, krum_m=3)
     perm = [4, 3, 2, 1, 0]          # the outlier first, best agents last
     # scores by position: [153.5, 2.5, 1.5, 1.0, 1.0] -> keep {3, 4, 2}
     assert agg.krum_select(U5[perm]).tolist() == [2, 3, 4]
@@ -79,13 +77,13 @@ def test_tie_break_prefers_lower_position():
     # two far-apart pairs of mutual nearest neighbours; K = 4, f = 1 -> c = 1,
     # score = distance to the nearest neighbour = 1 for every agent
     U = t64([[0, 0], [1, 0], [10, 0], [11, 0]])
-    agg, _ = make_agg(krum_f=1, krum_m=1)
+    agg = make_agg(krum_f=1, krum_m=1)
     assert torch.equal(agg.krum_scores(agg.pairwise_sqdist(U)),
                        t64([1, 1, 1, 1]))
     assert agg.krum_select(U).tolist() == [0]
-    agg, _ = make_agg(krum_f=1, krum_m=2)
+    agg = make_agg(krum_f=1, krum_m=2)
     assert agg.krum_select(U).tolist() == [0, 1]
-    agg, _ = make_agg(krum_f=1, krum_m=0)
+    agg = make_agg(krum_f=1, krum_m=0)
     assert agg.krum_select(U).tolist() == [0, 1, 2]
 
 
@@ -93,7 +91,7 @@ def test_duplicate_rows_skip_one_zero_only():
     # agents 0 and 1 are identical: each row of D holds two zeros, the sort
     # skips element 0 and the duplicate's zero is scored
     U = t64([[1, 1], [1, 1], [3, 1], [9, 9]])
-    agg, _ = make_agg(krum_f=1)
+    agg = make_agg(krum_f=1)
     D = agg.pairwise_sqdist(U)
     assert torch.equal(D, D.T) and D.diagonal().abs().sum() == 0
     assert torch.equal(agg.krum_scores(D), t64([0, 0, 4, 100]))
@@ -102,7 +100,7 @@ def test_duplicate_rows_skip_one_zero_only():
 def test_distance_matrix_structure_on_real_values():
     torch.manual_seed(0)
     U = torch.randn(9, 4099, dtype=torch.float64)
-    agg, _ = make_agg()
+    agg = make_agg()
     D = agg.pairwise_sqdist(U)
     assert torch.equal(D, D.T)
     assert (D.diagonal() == 0).all() and (D >= 0).all()
@@ -119,14 +117,14 @@ def test_distance_matrix_structure_on_real_values():
     (5, 1, -1, 'krum_m'),
 ])
 def test_validity_errors(K, f, m, word):
-    agg, args = make_agg()
-    args.krum_f, args.krum_m = f, m
+    agg = make_agg()
+    agg.args.krum_f, agg.args.krum_m = f, m
     with pytest.raises(ValueError, match=word):
         agg.agg_krum(torch.zeros(K, 2, dtype=torch.float64))
 
 
 def test_smallest_valid_case():
-    agg, _ = make_agg(krum_f=0, krum_m=0)          # K = 3: c = 1, m = 3
+    agg = make_agg(krum_f=0, krum_m=0)          # K = 3: c = 1, m = 3
     U = t64([[0, 0], [3, 0], [0, 6]])
     assert agg.krum_select(U).tolist() == [0, 1, 2]
     assert torch.equal(agg.agg_krum(U), t64([1, 2]))
@@ -190,18 +188,12 @@ def test_banner_line_only_for_krum(capsys):
 
 # ------------------------------------------------------------ server level
 
-class _P(torch.nn.Module):
-    def __init__(self, n):
-        super().__init__()
-        self.p = torch.nn.Parameter(torch.zeros(n))
-
-
 def test_rlr_with_krum_sign_flip():
     """Krum drops the outlier from the mean, yet the vote counts all K:
     a coordinate whose honest majority is too thin moves AGAINST the
     aggregate."""
     from rlr_amd.flatmodel import FlatParamModel
-    agg, _ = make_agg(n=2, krum_f=1, krum_m=0, robustLR_threshold=4)
+    agg = make_agg(n=2, krum_f=1, krum_m=0, robustLR_threshold=4)
     gm = FlatParamModel(_P(2), 'cpu')
     # K = 5; agent 4 is the outlier.  coord 0: all five positive, |vote| = 5.
     # coord 1: signs + + - - (+ from the outlier): |vote| = 1 < 4 -> flipped.
@@ -213,24 +205,17 @@ def test_rlr_with_krum_sign_flip():
     # coord 1 would flip under a vote over the four KEPT agents too
     # (|+1+1-1-1| = 0), so show the all-K property on coord 0: at theta = 5
     # only the excluded outlier's vote carries it over the threshold
-    agg, _ = make_agg(n=2, krum_f=1, krum_m=0, robustLR_threshold=5)
+    agg = make_agg(n=2, krum_f=1, krum_m=0, robustLR_threshold=5)
     gm = FlatParamModel(_P(2), 'cpu')
     agg.aggregate_updates(gm, U, cur_round=1, agent_ids=[0, 1, 2, 3, 4])
     assert gm.flat_params.tolist() == [1.0, 0.5]
 
 
 def test_corrupt_selected_is_logged():
-    class W:
-        def __init__(self):
-            self.rows = []
-
-        def add_scalar(self, name, v, step):
-            self.rows.append((name, v, step))
-
     from rlr_amd.flatmodel import FlatParamModel
     args = default_args(no_tb=True, aggr='krum', device='cpu', krum_f=1,
                         num_corrupt=2)
-    w = W()
+    w = Writer()
     agg = Aggregation({i: 1 for i in range(8)}, 2, None, args, writer=w)
     gm = FlatParamModel(_P(2), 'cpu')
     # sampled order 4, 1, 3, 0, 2 ; the outlier sits at position 0 (id 4)
@@ -250,7 +235,7 @@ def test_buffers_average_the_selection_unweighted():
             self.p = torch.nn.Parameter(torch.zeros(2))
             self.register_buffer('b', torch.zeros(3))
 
-    agg, _ = make_agg(n=2, krum_f=1, krum_m=0)
+    agg = make_agg(n=2, krum_f=1, krum_m=0)
     gm = FlatParamModel(BN(), 'cpu')
     ids = [0, 1, 2, 3, 4]
     agg.aggregate_updates(gm, U5, cur_round=1, agent_ids=ids)
@@ -274,42 +259,6 @@ def test_driver_runs_krum(tiny_args, tiny_sizes):
     assert torch.isfinite(h['final_params']).all()
     assert h['final_params'].shape == initial.shape
     assert not torch.equal(h['final_params'], initial)
-
-
-def _worker(rank, world_size, port, out_q):
-    os.environ['RANK'] = str(rank)
-    os.environ['WORLD_SIZE'] = str(world_size)
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    import rlr_amd.data.datasets as D
-    D.DEFAULT_SIZES['fmnist'] = (2000, 400)
-    from rlr_amd.federated import run
-    from rlr_amd.parallel import dist as pdist
-    args = default_args(num_agents=4, rounds=2, snap=2, local_ep=1, bs=64,
-                        synthetic=True, no_tb=True, data='fmnist',
-                        num_corrupt=1, poison_frac=0.5, aggr='krum',
-                        krum_f=1, robustLR_threshold=3, device='cpu')
-    try:
-        h = run(args)
-        if rank == 0:
-            out_q.put(h['final_params'].numpy().copy())
-    finally:
-        pdist.teardown()
-
-
-def _run_world(world_size):
-    ctx = mp.get_context('spawn')
-    q = ctx.Queue()
-    port = 29561 + world_size
-    procs = [ctx.Process(target=_worker, args=(r, world_size, port, q))
-             for r in range(world_size)]
-    for p in procs:
-        p.start()
-    params = q.get(timeout=300)
-    for p in procs:
-        p.join(timeout=120)
-        assert p.exitcode == 0
-    return torch.from_numpy(params)
 
 
 @pytest.mark.timeout(600)

@@ -6,6 +6,8 @@ Every test needs an MI355X: run with `pytest -m gpu`."""
 import pytest
 import torch
 
+from server_helpers import make_agg, randn
+
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
@@ -19,8 +21,7 @@ def ext():
 
 
 def _randn(K, n=N, seed=0):
-    g = torch.Generator().manual_seed(1000 * K + n + seed)
-    return torch.randn(K, n, dtype=torch.float64, generator=g).to(DEV)
+    return randn(K, n, seed).to(DEV)
 
 
 def _ints(K, n=N):
@@ -42,14 +43,6 @@ def cpu_trmean(U, b):
 def gpu_median(ext, U):
     m = (U.shape[0] - 1) // 2
     return ext.agg_orderstat(U, m, m + 1, False, 0.0, 0.0)[0]
-
-
-def make_agg(n, dev, **over):
-    from rlr_amd.aggregation import Aggregation
-    from rlr_amd.options import default_args
-    args = default_args(no_tb=True, device=dev, **over)
-    sizes = {i: 10 * (i + 1) for i in range(1024)}
-    return Aggregation(sizes, n, None, args)
 
 
 # ------------------------------------------------------------------ median

@@ -10,6 +10,9 @@ import functools
 import pytest
 import torch
 
+import server_helpers
+from server_helpers import P as _P
+
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda:0'
@@ -28,12 +31,7 @@ def ext():
     return _e()
 
 
-def make_agg(n, dev, **over):
-    from rlr_amd.aggregation import Aggregation
-    from rlr_amd.options import default_args
-    args = default_args(no_tb=True, device=dev, **over)
-    sizes = {i: 10 * (i + 1) for i in range(2048)}
-    return Aggregation(sizes, n, None, args)
+make_agg = functools.partial(server_helpers.make_agg, table=2048)
 
 
 def resolve(ext, K, n):
@@ -320,12 +318,6 @@ def test_argument_checks(ext):
 
 
 # ----------------------------------------------- end to end, both backends
-
-class _P(torch.nn.Module):
-    def __init__(self, n):
-        super().__init__()
-        self.p = torch.nn.Parameter(torch.zeros(n))
-
 
 E2E_K, E2E_N = 10, 4099
 

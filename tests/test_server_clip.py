@@ -5,35 +5,25 @@ the default-off identity, the boost, composition with krum and geomed,
 buffers, noise, logging and the run name."""
 
 import argparse
+import functools
 from fractions import Fraction
 from time import ctime
 
 import pytest
 import torch
 
-from rlr_amd.aggregation import Aggregation
 from rlr_amd.options import args_parser, default_args
 from rlr_amd.utils.logging import print_exp_details, run_name
+
+import server_helpers
+from server_helpers import P as _P, Writer, t64
 
 NEW_FLAGS = ('server_clip', 'server_clip_mode', 'attack_boost')
 # the issue's slack on a clipped norm: tau * (1 + 4 * 2^-52)
 SLACK = Fraction(4, 2 ** 52)
 
 
-def make_agg(n=4, writer=None, **over):
-    args = default_args(no_tb=True, device='cpu', **over)
-    sizes = {i: 10 * (i + 1) for i in range(1024)}
-    return Aggregation(sizes, n, None, args, writer=writer)
-
-
-def t64(rows):
-    return torch.tensor(rows, dtype=torch.float64)
-
-
-class _P(torch.nn.Module):
-    def __init__(self, n):
-        super().__init__()
-        self.p = torch.nn.Parameter(torch.zeros(n))
+make_agg = functools.partial(server_helpers.make_agg, n=4, dev='cpu')
 
 
 def exact_sq_norm(row):
@@ -428,23 +418,16 @@ def test_noise_std_follows_the_enforced_bound():
 
 
 def test_clip_scalars_are_logged():
-    class W:
-        def __init__(self):
-            self.rows = {}
-
-        def add_scalar(self, name, v, step):
-            self.rows[name] = (v, step)
-
     from rlr_amd.flatmodel import FlatParamModel
-    w = W()
+    w = Writer()
     agg = make_agg(writer=w, server_clip=5.0, num_corrupt=2)
     gm = FlatParamModel(_P(4), 'cpu')
     # ids 1 and 0 are corrupt: sampled positions 2 and 1, s = 0.5 and 1
     agg.aggregate_updates(gm, U_HAND, cur_round=6, agent_ids=[4, 0, 1])
-    assert w.rows['Clip/Bound'] == (5.0, 6)
-    assert w.rows['Clip/Frac_Clipped'][0] == pytest.approx(1 / 3)
-    assert w.rows['Clip/Corrupt_Scale_Mean'] == (0.75, 6)
-    assert all(isinstance(v, float) for v, _ in w.rows.values())
+    assert w.last['Clip/Bound'] == (5.0, 6)
+    assert w.last['Clip/Frac_Clipped'][0] == pytest.approx(1 / 3)
+    assert w.last['Clip/Corrupt_Scale_Mean'] == (0.75, 6)
+    assert all(isinstance(v, float) for v, _ in w.last.values())
 
 
 def test_dict_api_leaves_the_callers_tensors_alone():

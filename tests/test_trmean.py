@@ -1,20 +1,20 @@
 """Coordinate-wise trimmed-mean aggregation (--aggr trmean): closed-form
 cases, invariances, CLI surface and the driver, all on the CPU path."""
 
+import functools
 from time import ctime
 
 import pytest
 import torch
 
-from rlr_amd.aggregation import Aggregation
 from rlr_amd.options import args_parser, default_args
 from rlr_amd.utils.logging import run_name
 
+import server_helpers
 
-def make_agg(n=3, **over):
-    args = default_args(no_tb=True, aggr='trmean', **over)
-    sizes = {i: 10 * (i + 1) for i in range(32)}
-    return Aggregation(sizes, n, None, args), args
+
+make_agg = functools.partial(server_helpers.make_agg, n=3, aggr='trmean',
+                             table=32)
 
 
 # rows are agents, columns coordinates; every column is a permutation of a
@@ -31,7 +31,7 @@ U5 = torch.tensor([
 # ------------------------------------------------------------ closed form
 
 def test_closed_form_k5_b1():
-    agg, _ = make_agg(trim_frac=0.2)          # b = floor(0.2 * 5) = 1
+    agg = make_agg(trim_frac=0.2)          # b = floor(0.2 * 5) = 1
     out = agg.agg_trmean(U5)
     # sorted columns: [1,2,3,4,5], [-1,0,1,2,100], [-8,.125,.25,.5,4]
     expect = torch.tensor([(2.0 + 3.0 + 4.0) * (1.0 / 3),
@@ -42,7 +42,7 @@ def test_closed_form_k5_b1():
 
 
 def test_closed_form_b0_is_sorted_mean():
-    agg, _ = make_agg(trim_frac=0.0)
+    agg = make_agg(trim_frac=0.0)
     out = agg.agg_trmean(U5)
     expect = torch.tensor([15.0 * (1.0 / 5), 102.0 * (1.0 / 5),
                            ((((-8.0 + 0.125) + 0.25) + 0.5) + 4.0) * (1.0 / 5)],
@@ -57,7 +57,7 @@ def test_full_trim_equals_median(k):
     U = torch.randn(k, 101, dtype=torch.float64)
     b = (k - 1) // 2
     # (b + 0.25) / K floors to b and stays below 0.5 for every odd K
-    agg, _ = make_agg(n=101, trim_frac=(b + 0.25) / k)
+    agg = make_agg(n=101, trim_frac=(b + 0.25) / k)
     assert agg._trim_count(k) == b
     assert torch.equal(agg.agg_trmean(U), torch.median(U, dim=0).values)
 
@@ -67,7 +67,7 @@ def test_full_trim_equals_median(k):
 def test_permutation_invariance_bitwise():
     torch.manual_seed(1)
     U = torch.randn(11, 257, dtype=torch.float64) * 1e3
-    agg, _ = make_agg(n=257, trim_frac=0.2)
+    agg = make_agg(n=257, trim_frac=0.2)
     ref = agg.agg_trmean(U)
     g = torch.Generator().manual_seed(7)
     for _ in range(4):
@@ -83,7 +83,7 @@ def test_robust_to_two_outliers_where_avg_is_not():
     U[8, :32] = 1e6        # half the coordinates see two outliers on one side
     honest = U[[0, 1, 2, 4, 5, 6, 7, 9]]
     lo, hi = honest.min(dim=0).values, honest.max(dim=0).values
-    agg, _ = make_agg(n=64, trim_frac=0.2)
+    agg = make_agg(n=64, trim_frac=0.2)
     out = agg.agg_trmean(U)
     assert ((out >= lo) & (out <= hi)).all()
     avg = agg.agg_avg(U, list(range(10)))
@@ -99,7 +99,7 @@ def test_trim_frac_out_of_range_rejected_at_parse_time(bad):
 
 
 def test_k2_with_trim_049_keeps_both():
-    agg, _ = make_agg(n=2, trim_frac=0.49)
+    agg = make_agg(n=2, trim_frac=0.49)
     U = torch.tensor([[1.0, -4.0], [3.0, 2.0]], dtype=torch.float64)
     assert agg._trim_count(2) == 0
     assert torch.equal(agg.agg_trmean(U),
@@ -108,14 +108,14 @@ def test_k2_with_trim_049_keeps_both():
 
 def test_trim_never_empties_a_column():
     for frac in (0.0, 0.1, 0.25, 1 / 3, 0.49, 0.4999999):
-        agg, _ = make_agg(trim_frac=frac)
+        agg = make_agg(trim_frac=frac)
         for k in range(1, 21):
             assert k - 2 * agg._trim_count(k) >= 1, (frac, k)
 
 
 def test_trim_count_guard_message():
-    agg, args = make_agg()
-    args.trim_frac = 0.5       # past the parser's range check on purpose
+    agg = make_agg()
+    agg.args.trim_frac = 0.5       # past the parser's range check on purpose
     with pytest.raises(ValueError, match='trim_frac'):
         agg.agg_trmean(torch.zeros(4, 3, dtype=torch.float64))
 
@@ -163,7 +163,7 @@ def test_banner_prints_trim_fraction_only_for_trmean(capsys):
 def test_rlr_with_trmean_sign_flip():
     """Coordinates below the vote threshold move AGAINST the aggregate."""
     from rlr_amd.flatmodel import FlatParamModel
-    agg, _ = make_agg(n=2, robustLR_threshold=2)   # b = floor(0.1 * 2) = 0
+    agg = make_agg(n=2, robustLR_threshold=2)   # b = floor(0.1 * 2) = 0
 
     class M(torch.nn.Module):
         def __init__(self):
