@@ -9,8 +9,10 @@ per-parameter robust-learning-rate sign vote.  Build addition: the
 coordinate-wise trimmed mean (--aggr trmean, Yin et al. 2018), sharing one
 LDS sorting-network kernel family with the median at more than 64 sampled
 agents, Krum / Multi-Krum (--aggr krum, Blanchard et al. 2017) on an
-fp64 MFMA pairwise-distance kernel, and the geometric median / RFA
-(--aggr geomed, Pillutla et al.) on a fused Weiszfeld distance kernel; in
+fp64 MFMA pairwise-distance kernel, the geometric median / RFA
+(--aggr geomed, Pillutla et al.) on a fused Weiszfeld distance kernel, and
+Bulyan (--aggr bulyan, El Mhamdi et al. 2018), iterated Krum followed by a
+trimmed mean around the median on a fused select-and-trim kernel; in
 front of every rule, server-side norm clipping (--server_clip, Sun et al.)
 on a streaming row-norm kernel, and the boosted model-replacement attack
 (--attack_boost, Bagdasaryan et al.) it is the baseline defence against.

@@ -62,6 +62,44 @@ Rules (each a HIP kernel on the GPU path, ops/csrc/aggregation.hip):
     backends agree to rounding, not bit for bit (the sum over n is chunked
     on the GPU); each is a pure function of its input.  last_weights holds
     the final a normalised to sum 1.
+  * Bulyan (build addition, --aggr bulyan; El Mhamdi et al., "The Hidden
+    Vulnerability of Distributed Learning in Byzantium", 2018): the
+    agent-wise rule and the coordinate-wise rule composed.  With
+    f = --bulyan_f agents assumed Byzantine and K >= 4f + 3 sampled
+    (ValueError otherwise, checked per round):
+      stage 1, selection: theta = K - 2f - 2 agents by ITERATED Krum over
+        the one D = pairwise_sqdist(U).  All agents start alive; for
+        t = 0 .. theta-1 let r = K - t and c = r - f - 2; score[i] of an
+        alive agent sorts its distances to the other alive agents
+        ascending, adds the first c sequentially in ascending order and
+        multiplies by 1/c; the alive agent with the lowest score is selected
+        and removed, ties to the lowest sampled position (stable sort).
+        last_selected holds the theta positions ascending.  (The paper
+        writes theta = K - 2f, which runs Krum on as few as 2f + 1 agents,
+        below Krum's own 2f + 3; theta = K - 2f - 2 is what the authors'
+        implementation uses and keeps r >= 2f + 3, c >= f + 1 in every
+        iteration.)
+      stage 2, per coordinate: sort the theta selected values ascending
+        into s; m = (theta-1)//2, med = s[m] (the lower median, as comed
+        takes it); beta = theta - 2f = K - 4f - 2 >= 1; grow a window from
+        l = r = m, beta - 1 times:
+            dl = med - s[l-1]   (+inf when l == 0)
+            dr = s[r+1] - med   (+inf when r == theta-1)
+            dl <= dr ? l -= 1 : r += 1              TIES GO LEFT
+        agg = (s[l] + s[l+1] + ... + s[r]) * (1/beta), added sequentially
+        in ascending order in fp64.
+    Only subtractions, comparisons, ordered adds and one multiply: CPU and
+    GPU agree bit for bit given the same selection, and the result does not
+    depend on the agent order.  f = 0 selects K - 2 agents and averages all
+    of them.  On the GPU the selection loop runs on device tensors without
+    a host sync (a working copy of D whose dead rows and columns are +inf,
+    scores from the order-statistic kernel, exactly krum's) and stage 2 is
+    bulyan_k in ops/csrc/orderstat.hip: without noise ONE fused kernel
+    sorts the selected rows in LDS, takes the vote over ALL K rows and
+    applies.  Noise behaves as for trmean (the composed path only);
+    --server_clip runs in front unchanged; BatchNorm buffers take the
+    unweighted mean over the theta selected agents.  Non-finite updates are
+    out of scope.
   * sign (aggregation.py:71-75): sign(sum_k sign(U_k)).
   * server-side norm clipping (build addition, --server_clip > 0; Sun et
     al., "Can You Really Backdoor Federated Learning?", and the clipping
@@ -114,6 +152,36 @@ def _row_sum(rows, w=None):
     return out
 
 
+def bulyan_window_mean(rows, beta):
+    """Stage 2 of Bulyan in plain torch — THE CPU rule (module docstring):
+    per column of rows (theta, n) the mean of the beta sorted values
+    nearest the lower median, the window grown one step at a time with ties
+    going left, summed in ascending order."""
+    theta, n = rows.shape
+    if not 1 <= beta <= theta:
+        raise ValueError(f"beta={beta} must be in [1, theta] = [1, {theta}]")
+    s = torch.sort(rows, dim=0).values
+    col = torch.arange(n, device=rows.device)
+    m = (theta - 1) // 2
+    med = s[m]
+    inf = torch.full_like(med, float('inf'))
+    l = torch.full((n,), m, dtype=torch.long, device=rows.device)
+    r = l.clone()
+    for _ in range(beta - 1):
+        dl = torch.where(l > 0, med - s[(l - 1).clamp(min=0), col], inf)
+        dr = torch.where(r < theta - 1,
+                         s[(r + 1).clamp(max=theta - 1), col] - med, inf)
+        # beta <= theta keeps one side open; the edge tests keep l and r in
+        # range for non-finite input too
+        left = (r == theta - 1) | ((l > 0) & (dl <= dr))
+        l = l - left.long()
+        r = r + (~left).long()
+    out = torch.zeros(n, dtype=rows.dtype, device=rows.device)
+    for i in range(beta):
+        out += s[l + i, col]
+    return out * (1.0 / beta)
+
+
 class Aggregation:
     def __init__(self, agent_data_sizes, n_params, poisoned_val_loader,
                  args, writer=None):
@@ -124,7 +192,8 @@ class Aggregation:
         self.n_params = n_params
         self.poisoned_val_loader = poisoned_val_loader
         self.cum_net_mov = 0.0
-        self.last_selected = None   # krum: sampled positions kept last round
+        # krum, bulyan: sampled positions kept last round
+        self.last_selected = None
         self.last_weights = None    # geomed: final weights, normalised
         # server_clip: last round's factors s (K), bound tau (0-d) and
         # pre-clip norms (K), on the updates' device
@@ -152,7 +221,7 @@ class Aggregation:
             stacked = self.server_clip_updates(stacked)
             self._log_clip(agent_ids, cur_round)
 
-        rule, w, span = self._resolve(stacked, agent_ids, cur_round)
+        rule, w, span, subset = self._resolve(stacked, agent_ids, cur_round)
         K = stacked.shape[0]
         rlr = self.args.robustLR_threshold > 0
 
@@ -181,6 +250,19 @@ class Aggregation:
                 False)
             return
 
+        if (_gpu(stacked) and subset is not None and self.args.noise == 0
+                and K <= ext().bulyan_max_k()):
+            # bulyan: ONE fused kernel sorts the selected rows of each
+            # column in LDS, trims around their median, takes the vote over
+            # all K rows and applies
+            sel, theta, beta = subset
+            ext().bulyan_rlr_apply(
+                stacked, self._bulyan_perm(sel, K), theta, beta,
+                global_model.flat_params, rlr,
+                float(self.args.robustLR_threshold), float(self.server_lr),
+                False)
+            return
+
         # composed path: vote, rule, noise, apply
         lr_vector = self.compute_robustLR(stacked) if rlr else None
         agg = rule(stacked)
@@ -190,30 +272,40 @@ class Aggregation:
 
     def _resolve(self, stacked, agent_ids, cur_round):
         """What --aggr decides for this round, looked at in this one place:
-        (rule, weights, span).  weights: for a weighted mean of the rows;
-        span: [lo, hi) of each sorted column to average; neither for sign.
+        (rule, weights, span, subset).  weights: for a weighted mean of the
+        rows; span: [lo, hi) of each sorted column to average; subset:
+        (selected positions, theta, beta) for bulyan's trimmed mean around
+        the median of the selected rows; none of them for sign.
         rule(stacked) is the aggregate as the composed path computes it.
         Sets last_selected / last_weights and logs what the rule chose."""
         aggr, K, dev = self.args.aggr, stacked.shape[0], stacked.device
         if aggr == 'avg':
             w = self._weights(agent_ids, dev)
-            return (lambda U: self._mean(U, w, self._avg_mean)), w, None
+            return (lambda U: self._mean(U, w, self._avg_mean)), w, None, None
         if aggr == 'krum':
             self.last_selected = self.krum_select(stacked)
             self._log_krum(agent_ids, cur_round)
             w = self._krum_weights(K, dev)
-            return (lambda U: self._mean(U, w, self._krum_mean)), w, None
+            return ((lambda U: self._mean(U, w, self._krum_mean)), w, None,
+                    None)
         if aggr == 'geomed':
             a = self.geomed_weights(stacked)
             self.last_weights = a / a.sum()
             self._log_geomed(agent_ids, cur_round)
-            return (lambda U: self._mean(U, a, self._geomed_mean)), a, None
+            return ((lambda U: self._mean(U, a, self._geomed_mean)), a, None,
+                    None)
+        if aggr == 'bulyan':
+            theta, beta = self._bulyan_counts(K)
+            sel = self.last_selected = self.bulyan_select(stacked)
+            self._log_bulyan(agent_ids, cur_round)
+            return ((lambda U: self._bulyan_trim(U, sel)), None, None,
+                    (sel, theta, beta))
         if aggr == 'comed':
-            return self.agg_comed, None, self._comed_span(K)
+            return self.agg_comed, None, self._comed_span(K), None
         if aggr == 'trmean':
-            return self.agg_trmean, None, self._trim_span(K)
+            return self.agg_trmean, None, self._trim_span(K), None
         if aggr == 'sign':
-            return self.agg_sign, None, None
+            return self.agg_sign, None, None, None
         raise ValueError(aggr)
 
     # ------------------------------------------------------- server clip
@@ -417,6 +509,80 @@ class Aggregation:
                         if agent_ids[p] < self.args.num_corrupt)
             self.writer.add_scalar('Krum/Corrupt_Selected', n_bad, cur_round)
 
+    # ------------------------------------------------------------ bulyan
+
+    def _bulyan_counts(self, K):
+        """(theta, beta): agents selected, values averaged per coordinate."""
+        f = self.args.bulyan_f
+        if f < 0 or K < 4 * f + 3:
+            raise ValueError(
+                f"bulyan_f={f} needs K >= 4 f + 3 = {4 * f + 3} sampled "
+                f"agents, got K={K}")
+        return K - 2 * f - 2, K - 4 * f - 2
+
+    def bulyan_picks(self, D):
+        """Stage 1 given the distances D (K, K): iterated Krum, the theta
+        selected positions ascending.  One loop for both backends and no
+        host sync in it: dead rows and columns of the working copy are
+        +inf, so a dead agent scores +inf and an alive one, whose sorted
+        column is its own 0, the alive others and then +inf, scores exactly
+        the rule's sum.  The scores are krum_scores' on either backend."""
+        K = D.shape[0]
+        f = self.args.bulyan_f
+        theta, _ = self._bulyan_counts(K)
+        Dw = D.clone(memory_format=torch.contiguous_format)
+        kernel = _gpu(D) and K <= ext().orderstat_max_k()
+        picks = []
+        for t in range(theta):
+            c = K - t - f - 2
+            if kernel:
+                scores = ext().agg_orderstat(Dw, 1, c + 1, False, 0.0, 0.0)[0]
+            else:
+                scores = (_row_sum(torch.sort(Dw, dim=0).values[1:c + 1])
+                          * (1.0 / c))
+            win = torch.sort(scores, stable=True).indices[:1]
+            Dw.index_fill_(0, win, float('inf'))
+            Dw.index_fill_(1, win, float('inf'))
+            picks.append(win)
+        return torch.sort(torch.cat(picks)).values
+
+    def bulyan_select(self, stacked):
+        """Sampled positions of the theta agents iterated Krum selects,
+        ascending."""
+        self._bulyan_counts(stacked.shape[0])
+        return self.bulyan_picks(self.pairwise_sqdist(stacked))
+
+    @staticmethod
+    def _bulyan_perm(sel, K):
+        """The K row indices as int32, the selected ones first (both parts
+        ascending), built on sel's device without a host sync."""
+        rest = torch.ones(K, dtype=torch.int8, device=sel.device)
+        rest[sel] = 0
+        return torch.sort(rest, stable=True).indices.to(torch.int32)
+
+    def _bulyan_trim(self, stacked, sel):
+        """Stage 2 over the rows sel of stacked."""
+        K = stacked.shape[0]
+        theta, beta = self._bulyan_counts(K)
+        if _gpu(stacked) and K <= ext().bulyan_max_k():
+            return ext().bulyan_trim(stacked, self._bulyan_perm(sel, K),
+                                     theta, beta, False, 0.0, 0.0)[0]
+        # the CPU rule; above the kernel's K limit the same on the device
+        return bulyan_window_mean(stacked[sel], beta)
+
+    def agg_bulyan(self, stacked):
+        """Bulyan aggregate of the updates (module docstring), fp64.
+        Remembers the selection in last_selected."""
+        self.last_selected = self.bulyan_select(stacked)
+        return self._bulyan_trim(stacked, self.last_selected)
+
+    def _log_bulyan(self, agent_ids, cur_round):
+        if self.writer:
+            n_bad = sum(1 for p in self.last_selected.tolist()
+                        if agent_ids[p] < self.args.num_corrupt)
+            self.writer.add_scalar('Bulyan/Corrupt_Selected', n_bad,
+                                   cur_round)
+
     # ------------------------------------------------------------ geomed
 
     def _geomed_loop(self, stacked):
@@ -500,7 +666,7 @@ class Aggregation:
         """What the rule last decided about the agents, read back from
         last_selected / last_weights; data sizes for the rules that decide
         nothing about them."""
-        if self.args.aggr == 'krum':
+        if self.args.aggr in ('krum', 'bulyan'):
             return self._krum_weights(len(agent_ids), device)
         if self.args.aggr == 'geomed':
             return self.last_weights.to(device)
@@ -508,8 +674,8 @@ class Aggregation:
 
     def aggregate_buffers(self, global_model, buffer_deltas, agent_ids):
         """FedAvg-BN: data-weighted mean of BatchNorm running-stat deltas
-        (build extension — the reference has no BN).  Under krum: the
-        unweighted mean over the agents selected for the parameters.  Under
+        (build extension — the reference has no BN).  Under krum and bulyan:
+        the unweighted mean over the agents selected for the parameters.  Under
         --server_clip agent k's delta is first multiplied by the s[k] its
         update was clipped with."""
         if global_model.n_buffers == 0 or buffer_deltas is None:

@@ -722,6 +722,48 @@ torch::Tensor orderstat_rlr_apply(torch::Tensor U, int64_t lo, int64_t hi,
   return lr;
 }
 
+// perm: K distinct row indices of U, the theta selected rows first.  Its
+// values live on the device; the kernel never dereferences one outside
+// [0, K).
+static void check_bulyan(const torch::Tensor& U, const torch::Tensor& perm,
+                         int64_t theta, int64_t beta) {
+  check_matrix(U, bulyan_max_k());
+  check_vector(perm, U, U.size(0), torch::kInt32);
+  CHK(1 <= beta && beta <= theta && theta <= U.size(0));
+}
+
+std::tuple<torch::Tensor, torch::Tensor> bulyan_trim(
+    torch::Tensor U, torch::Tensor perm, int64_t theta, int64_t beta,
+    bool want_lr, double thresh, double slr) {
+  check_bulyan(U, perm, theta, beta);
+  int K = U.size(0);
+  long n = U.size(1);
+  auto out = torch::empty({n}, U.options());
+  auto lr = lr_buf(want_lr, n, U);
+  launch_bulyan_trim(U.data_ptr<double>(), perm.data_ptr<int>(), K,
+                     (int)theta, (int)beta, n, out.data_ptr<double>(),
+                     want_lr ? lr.data_ptr<double>() : nullptr, thresh, slr,
+                     stream_of(U));
+  return {out, lr};
+}
+
+torch::Tensor bulyan_rlr_apply(torch::Tensor U, torch::Tensor perm,
+                               int64_t theta, int64_t beta,
+                               torch::Tensor params, bool rlr, double thresh,
+                               double slr, bool want_lr) {
+  check_bulyan(U, perm, theta, beta);
+  check_vector(params, U, U.size(1), torch::kFloat32);
+  int K = U.size(0);
+  long n = U.size(1);
+  auto lr = lr_buf(want_lr, n, U);
+  launch_bulyan_rlr_apply(U.data_ptr<double>(), perm.data_ptr<int>(), K,
+                          (int)theta, (int)beta, n, rlr ? 1 : 0, thresh, slr,
+                          params.data_ptr<float>(),
+                          want_lr ? lr.data_ptr<double>() : nullptr,
+                          stream_of(U));
+  return lr;
+}
+
 torch::Tensor pairwise_sqdist(torch::Tensor U) {
   check_matrix(U, pairdist_max_k());
   int K = U.size(0);
@@ -1576,6 +1618,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("agg_orderstat", &agg_orderstat);
   m.def("orderstat_rlr_apply", &orderstat_rlr_apply);
   m.def("orderstat_max_k", &orderstat_max_k);
+  m.def("bulyan_trim", &bulyan_trim);
+  m.def("bulyan_rlr_apply", &bulyan_rlr_apply);
+  m.def("bulyan_max_k", &bulyan_max_k);
   m.def("pairwise_sqdist", &pairwise_sqdist);
   m.def("pairdist_max_k", &pairdist_max_k);
   m.def("pairdist_chunks", &pairdist_chunks);

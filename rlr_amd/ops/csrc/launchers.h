@@ -237,6 +237,17 @@ void launch_orderstat_rlr_apply(const double* U, int K, long n, int lo,
                                 int hi, double inv_cnt, int mode_rlr,
                                 double thresh, double slr, float* params,
                                 double* lr_out, void* s);
+// Bulyan's trimmed mean around the median of the rows perm[0..theta) of U,
+// vote over all K rows; perm: K distinct row indices on the device,
+// 1 <= beta <= theta <= K <= bulyan_max_k() (lr_out is nullable)
+int bulyan_max_k();
+void launch_bulyan_trim(const double* U, const int* perm, int K, int theta,
+                        int beta, long n, double* out, double* lr_out,
+                        double thresh, double slr, void* s);
+void launch_bulyan_rlr_apply(const double* U, const int* perm, int K,
+                             int theta, int beta, long n, int mode_rlr,
+                             double thresh, double slr, float* params,
+                             double* lr_out, void* s);
 // pairdist.hip: D (K, K) = squared L2 distances between the rows of U
 // (K, n), 1 <= K <= pairdist_max_k().  Stage 1 splits n into
 // pairdist_chunks(K, n) chunks (a pure function of K and n) and writes one

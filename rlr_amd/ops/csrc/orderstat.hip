@@ -33,6 +33,10 @@
 // The RLR vote comes from the resident tile: each lane counts the signs of
 // the rows it loads, the L partial counts meet in LDS.  Sums of +-1 are
 // exact in any order, so lr is bitwise rlr_vote_k's.
+//
+// bulyan_k below is the sibling for Bulyan's second stage: the same network
+// over a device-chosen subset of the rows and a per-column window around
+// the subset's median instead of the fixed span.
 #include "common.h"
 #include "launchers.h"
 
@@ -237,6 +241,152 @@ static void launch_orderstat(const double* U, int K, long n, int lo, int hi,
                             thresh, slr, out, params, lr_out);
 }
 
+// ------------------------------------------------------------- Bulyan
+// Stage 2 of Bulyan (El Mhamdi et al., 2018) on the same network: the tile
+// holds only the theta SELECTED rows, row i < theta of the tile being row
+// perm[i] of U (perm: K distinct row indices, selected first), padded to
+// P = pow2 >= theta with +inf.  The rows perm[theta..K) are read in the same
+// load loop for their sign alone, so every element of U still comes from
+// HBM once and the vote is over all K rows.  perm is staged in LDS once per
+// block.  After the sort lane 0 of each column grows a window of beta
+// values around the lower median s[m], m = (theta - 1) / 2, always taking
+// the nearer neighbour and the LEFT one on a tie,
+//     dl = med - s[l-1]  (+inf at l == 0)
+//     dr = s[r+1] - med  (+inf at r == theta - 1)
+//     dl <= dr ? --l : ++r                         beta - 1 times
+// and reads off agg = (s[l] + ... + s[r]) * inv_beta, sequentially in
+// ascending order.  Subtractions, comparisons, ordered adds and one
+// multiply: bitwise the CPU rule.  (Lane 0 finds the window's left end by
+// bisection over the same differences instead of stepping; see there.)  A perm entry outside [0, K) (the binding
+// cannot see the values) is never dereferenced: its row reads as padding.
+constexpr int kBulyanMaxK = 512;      // tile 128 KiB + votes 4 KiB + perm 2 KiB
+
+template <int MODE>
+__global__ void bulyan_k(const double* __restrict__ U,
+                         const int* __restrict__ perm, int K, int theta,
+                         int beta, int lgP, int L, int TB, long n,
+                         double inv_beta, int mode_rlr, double thresh,
+                         double slr, double* __restrict__ out,
+                         float* __restrict__ params,
+                         double* __restrict__ lr_out) {
+  extern __shared__ double smem[];
+  const int P = 1 << lgP;
+  const int c = threadIdx.x % kTile;
+  const int j = (threadIdx.x / kTile) % L;
+  const int sub = threadIdx.x / (kTile * L);
+  double* s = smem + (long)sub * P * kTile;            // [TB][P][kTile]
+  int* part = (int*)(smem + (long)TB * P * kTile)      // [TB][L][kTile]
+              + sub * L * kTile;                       // partial votes
+  int* prm = (int*)(smem + (long)TB * P * kTile)       // [K], block-wide
+             + TB * L * kTile;
+  const bool vote = (MODE == 1) ? (mode_rlr != 0) : (lr_out != nullptr);
+  const long tiles = (n + kTile - 1) / kTile;
+  const int rows = K > P ? K : P;       // load trips: tile rows and sign rows
+
+  for (int k = threadIdx.x; k < K; k += blockDim.x) prm[k] = perm[k];
+  __syncthreads();
+
+  // the trip count is uniform over the block: barriers inside
+  for (long t0 = (long)blockIdx.x * TB; t0 < tiles;
+       t0 += (long)gridDim.x * TB) {
+    const long col = (t0 + sub) * kTile + c;
+    const bool live = col < n;
+
+    // coalesced tile load (a half-wave reads 256 contiguous bytes of a row)
+    int v = 0;
+    for (int k = j; k < rows; k += L) {
+      double u = INFINITY;
+      if (k < K && live) {
+        const int row = prm[k];
+        if ((unsigned)row < (unsigned)K) {
+          const double x = U[(long)row * n + col];
+          v += (x > 0.0) ? 1 : (x < 0.0 ? -1 : 0);
+          if (k < theta) u = x;
+        }
+      }
+      if (k < P) s[k * kTile + c] = u;
+    }
+    if (vote) part[j * kTile + c] = v;
+    __syncthreads();
+
+    NetPass t = {0, 0, 0, false};
+    while (net_next(lgP, t)) {
+      net_pass_n(s, c, j, L, P, t);
+      __syncthreads();
+    }
+
+    if (j == 0 && live) {
+      const int m = (theta - 1) / 2;
+      const double med = s[m * kTile + c];
+      // The window's beta - 1 steps merge the two ascending sequences
+      // dl(a) = med - s[m-a] and dr(b) = s[m+b] - med (rounded differences
+      // of a sorted column stay ordered), left first on a tie.  The a-th
+      // left value is among the first beta - 1 merged iff fewer than
+      // beta - a right values are strictly nearer, i.e. iff
+      // dl(a) <= dr(beta - a); that is monotone in a, so the number of
+      // left steps is found by bisection: ~log2(beta) dependent LDS reads
+      // instead of beta - 1.  [lo, hi] keeps both ends inside the theta
+      // rows whatever the data.
+      int lo = beta - 1 - (theta - 1 - m);
+      if (lo < 0) lo = 0;
+      int hi = beta - 1 < m ? beta - 1 : m;
+      while (lo < hi) {
+        const int a = (lo + hi + 1) >> 1;     // lo < a <= hi <= m
+        const double dl = med - s[(m - a) * kTile + c];
+        const double dr = s[(m + beta - a) * kTile + c] - med;  // <= theta-1
+        if (dl <= dr) lo = a; else hi = a - 1;
+      }
+      const int l = m - lo, r = l + beta - 1;
+      double acc = 0.0;
+      for (int i = l; i <= r; ++i) acc += s[i * kTile + c];
+      double agg = acc * inv_beta;
+      double lr = slr;
+      if (vote) {
+        int vs = 0;
+        for (int q = 0; q < L; ++q) vs += part[q * kTile + c];
+        lr = (fabs((double)vs) >= thresh) ? slr : -slr;
+      }
+      if (lr_out) lr_out[col] = lr;
+      if (MODE == 0) {
+        out[col] = agg;
+      } else {
+        params[col] = (float)((double)params[col] + lr * agg);
+      }
+    }
+    __syncthreads();  // tile is overwritten by the next iteration's load
+  }
+}
+
+// Block shapes as launch_orderstat's, sized by theta: the tile holds theta
+// rows, whatever K is.
+template <int MODE>
+static void launch_bulyan(const double* U, const int* perm, int K, int theta,
+                          int beta, long n, int mode_rlr, double thresh,
+                          double slr, double* out, float* params,
+                          double* lr_out, hipStream_t st) {
+  int lgP = 0;
+  while ((1 << lgP) < theta) ++lgP;
+  int P = 1 << lgP;
+  int L = P >> kPassBits;
+  if (L < 1) L = 1;
+  if (L > kOrderstatMaxLanes) L = kOrderstatMaxLanes;
+  int TB = kBlock / (kTile * L);
+  if (TB < 1) TB = 1;
+  size_t lds = (size_t)TB * P * kTile * sizeof(double)
+               + (size_t)TB * L * kTile * sizeof(int)
+               + (size_t)K * sizeof(int);
+  if (lds > 64 * 1024) {
+    HIP_CHECK(hipFuncSetAttribute(
+        (const void*)bulyan_k<MODE>,
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+  long tiles = (n + kTile - 1) / kTile;
+  bulyan_k<MODE><<<grid_for((tiles + TB - 1) / TB, 1), TB * L * kTile, lds,
+                   st>>>(U, perm, K, theta, beta, lgP, L, TB, n,
+                         1.0 / (double)beta, mode_rlr, thresh, slr, out,
+                         params, lr_out);
+}
+
 extern "C" {
 int orderstat_max_k() { return kOrderstatMaxK; }
 
@@ -254,5 +404,23 @@ void launch_orderstat_rlr_apply(const double* U, int K, long n, int lo,
                                 double* lr_out /*nullable*/, void* s) {
   launch_orderstat<1>(U, K, n, lo, hi, inv_cnt, mode_rlr, thresh, slr,
                       nullptr, params, lr_out, (hipStream_t)s);
+}
+
+int bulyan_max_k() { return kBulyanMaxK; }
+
+void launch_bulyan_trim(const double* U, const int* perm, int K, int theta,
+                        int beta, long n, double* out,
+                        double* lr_out /*nullable*/, double thresh,
+                        double slr, void* s) {
+  launch_bulyan<0>(U, perm, K, theta, beta, n, 0, thresh, slr, out, nullptr,
+                   lr_out, (hipStream_t)s);
+}
+
+void launch_bulyan_rlr_apply(const double* U, const int* perm, int K,
+                             int theta, int beta, long n, int mode_rlr,
+                             double thresh, double slr, float* params,
+                             double* lr_out /*nullable*/, void* s) {
+  launch_bulyan<1>(U, perm, K, theta, beta, n, mode_rlr, thresh, slr,
+                   nullptr, params, lr_out, (hipStream_t)s);
 }
 }

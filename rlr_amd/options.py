@@ -33,9 +33,9 @@ def args_parser(argv=None):
                         help="number of communication rounds R")
     parser.add_argument('--aggr', type=str, default='avg',
                         choices=['avg', 'comed', 'sign', 'trmean', 'krum',
-                                 'geomed'],
-                        help="aggregation rule (trmean, krum and geomed are "
-                             "build additions)")
+                                 'geomed', 'bulyan'],
+                        help="aggregation rule (trmean, krum, geomed and "
+                             "bulyan are build additions)")
     parser.add_argument('--local_ep', type=int, default=2,
                         help="number of local epochs E")
     parser.add_argument('--bs', type=int, default=256,
@@ -80,6 +80,9 @@ def args_parser(argv=None):
     parser.add_argument('--krum_m', type=int, default=0,
                         help="number of agents Krum keeps: 1 = classic Krum, "
                              "0 = K - krum_f (Multi-Krum)")
+    parser.add_argument('--bulyan_f', type=int, default=1,
+                        help="number of sampled agents assumed Byzantine; "
+                             "needs K >= 4 f + 3 (--aggr bulyan)")
     parser.add_argument('--geomed_iters', type=int, default=8,
                         help="smoothed Weiszfeld iterations; 0 = the "
                              "unweighted mean (--aggr geomed)")
@@ -159,8 +162,9 @@ def finalize_args(args):
     (reference federated.py:23); 0 <= trim_frac < 0.5 so that at least one
     value per coordinate survives the trim for every K; krum_f, krum_m >= 0
     (their upper limits depend on the sampled K and are checked by the
-    server); geomed_iters >= 0 and geomed_nu > 0; server_clip >= 0 with a
-    known mode; attack_boost > 0."""
+    server); bulyan_f >= 0 (K >= 4 bulyan_f + 3 likewise by the server);
+    geomed_iters >= 0 and geomed_nu > 0; server_clip >= 0 with a known mode;
+    attack_boost > 0."""
     args.server_lr = args.server_lr if args.aggr == 'sign' else 1.0
     if not 0 <= args.trim_frac < 0.5:
         raise ValueError(
@@ -169,6 +173,8 @@ def finalize_args(args):
         raise ValueError(
             f"--krum_f and --krum_m must be >= 0, got {args.krum_f} and "
             f"{args.krum_m}")
+    if args.bulyan_f < 0:
+        raise ValueError(f"--bulyan_f must be >= 0, got {args.bulyan_f}")
     check_geomed(args.geomed_iters, args.geomed_nu)
     check_server_clip(args.server_clip, args.server_clip_mode)
     if not 0 < args.attack_boost < float('inf'):

@@ -7,9 +7,9 @@ from time import ctime
 
 
 def run_name(args):
-    """Reference federated.py:27-30 run-name string; the trimmed mean, krum
-    and geomed (build additions) append their own flags, every other rule
-    keeps the reference name byte for byte.  Server-side clipping and the
+    """Reference federated.py:27-30 run-name string; the trimmed mean, krum,
+    geomed and bulyan (build additions) append their own flags, every other
+    rule keeps the reference name byte for byte.  Server-side clipping and the
     attack boost (build additions) append theirs only when switched on."""
     name = (f"time:{ctime()}-clip_val:{args.clip}-noise_std:{args.noise}"
             f"-aggr:{args.aggr}-s_lr:{args.server_lr}-num_cor:{args.num_corrupt}"
@@ -21,6 +21,8 @@ def run_name(args):
         name += f"-krum_f:{args.krum_f}-krum_m:{args.krum_m}"
     if args.aggr == 'geomed':
         name += f"-gm_iters:{args.geomed_iters}-gm_nu:{args.geomed_nu}"
+    if args.aggr == 'bulyan':
+        name += f"-bulyan_f:{args.bulyan_f}"
     if getattr(args, 'server_clip', 0) > 0:
         name += f"-sclip:{args.server_clip}-{args.server_clip_mode}"
     if getattr(args, 'attack_boost', 1.0) != 1.0:
@@ -51,6 +53,8 @@ def print_exp_details(args):
     if args.aggr == 'geomed':
         print(f'    Geomed iters / nu: {args.geomed_iters} / '
               f'{args.geomed_nu}')
+    if args.aggr == 'bulyan':
+        print(f'    Bulyan f: {args.bulyan_f}')
     if getattr(args, 'server_clip', 0) > 0:
         print(f'    Server Clip: {args.server_clip} '
               f'({args.server_clip_mode})')
