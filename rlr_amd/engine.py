@@ -12,7 +12,8 @@ Y[sel] into the static input buffers (ops/csrc/step_batch.hip).  The
 dropout-state advance is the last role of the captured step (the philox
 seed/offset pair lives in DEVICE memory precisely so replays draw fresh
 masks — ops/functional.DropoutCtx).  The fp32 CNN_MNIST step is 19 launches:
-18 in the graph (weight prep, 2 conv fwd, seam fwd, fc1 GEMM + partial +
+18 in the graph (weight prep, 2 conv fwd, the second one pooling in its
+epilogue, seam fwd from the pooled image, fc1 GEMM + partial +
 reduce, head rows, 2 fc1 bwd GEMMs, seam bwd, bwd-data, 2 bwd-weight
 partial kernels, the 2 batched fold levels, 2 optimizer kernels) and the
 feed (1 + 2 + 1 + 3 + 1 + 2 + 1 + 1 + 2 + 2 + 2 = 18).  With

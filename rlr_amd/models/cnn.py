@@ -105,10 +105,14 @@ class CNN_MNIST(_OpsModel):
             (self.conv2.weight, 1)))
         a1 = E.conv2d_fwd(x, self.conv1.weight, self.conv1.bias, 1, 0, True,
                           wt1)
-        a2 = E.conv2d_fwd(a1, self.conv2.weight, self.conv2.bias, 1, 0, True,
-                          wt2)
-        # pool + flatten + dropout-1 in one kernel (ops/csrc/fused_tail.hip)
-        pl, idx, d1, m1 = E.pool_flatten_dropout_fwd(a2, p, st, 0)
+        # conv2 pools in its own epilogue (ops/csrc/conv_f32.hip): its
+        # full-size output a2 is never stored, only its shape is kept
+        pl, idx = E.conv2d_pool_fwd(a1, self.conv2.weight, self.conv2.bias,
+                                    1, 0, wt2)
+        a2_shape = [a1.shape[0], self.conv2.weight.shape[0],
+                    a1.shape[2] - 2, a1.shape[3] - 2]
+        # flatten + dropout-1 in one kernel (ops/csrc/fused_tail.hip)
+        d1, m1 = E.flatten_dropout_fwd(pl, p, st, 0)
         h1 = E.linear_fwd(d1, self.fc1.weight, self.fc1.bias, True)
 
         # Backward with the relu masks FUSED away (each bitwise-identical
@@ -126,8 +130,7 @@ class CNN_MNIST(_OpsModel):
         g = E.linear_bwd_into(d1, self.fc1.weight, g,
                               self.fc1.weight.grad, self.fc1.bias.grad, True,
                               q)
-        g = E.dropout_unflatten_pool_bwd_relu(g, m1, idx, pl, p,
-                                              list(a2.shape))
+        g = E.dropout_unflatten_pool_bwd_relu(g, m1, idx, pl, p, a2_shape)
         g = E.conv2d_bwd_into(a1, self.conv2.weight, g, 1, 0, True,
                               self.conv2.weight.grad, self.conv2.bias.grad,
                               a1, wp2, q)

@@ -1043,6 +1043,27 @@ pool_flatten_dropout_fwd(torch::Tensor a, double p, torch::Tensor state,
   return {pooled, idx, d, mask};
 }
 
+// flatten (CHW order) + dropout of an already pooled channels_last image
+// (conv2d_pool_fwd's): -> (d, mask), what pool_flatten_dropout_fwd returns
+// for them
+std::tuple<torch::Tensor, torch::Tensor> flatten_dropout_fwd(
+    torch::Tensor pooled, double p, torch::Tensor state, int64_t site) {
+  TORCH_CHECK(pooled.is_cuda() && pooled.dim() == 4 && !is_bf16(pooled));
+  int Nb = pooled.size(0), C = pooled.size(1), OH = pooled.size(2),
+      OW = pooled.size(3);
+  if (!pool_seam_fused_ok(C, 2 * OH, 2 * OW))
+    return dropout_fwd_dev(nhwc_flatten(pooled), p, state, site);
+  pooled = cl(pooled, "seam_fwd.pooled");
+  auto d = torch::empty({Nb, (int64_t)C * OH * OW}, pooled.options());
+  auto mask = torch::empty({Nb, (int64_t)C * OH * OW},
+                           pooled.options().dtype(torch::kUInt8));
+  launch_flatten_dropout_fwd(pooled.data_ptr<float>(), d.data_ptr<float>(),
+                             mask.data_ptr<uint8_t>(), Nb, OH, OW, C,
+                             (float)p, dropout_state(state), (int)site,
+                             stream_of(pooled));
+  return {d, mask};
+}
+
 // dropout backward + unflatten + maxpool backward with the relu mask of
 // the pooled values: g (B, C*OH*OW) -> dx, channels_last of x_shape
 torch::Tensor dropout_unflatten_pool_bwd_relu(torch::Tensor g,
@@ -1176,6 +1197,41 @@ torch::Tensor conv2d_fwd(torch::Tensor x, torch::Tensor w,
                   y.data_ptr<float>(), Nb, C, H, W, Kout, R, S, OH, OW,
                   (int)stride, (int)pad, relu ? 1 : 0, stream_of(x));
   return y;
+}
+
+// conv + bias + relu + maxpool2x2 (fp32): -> (pooled, idx), what
+// maxpool2x2_fwd(conv2d_fwd(..., relu=true)) returns.  One kernel where
+// conv_pool_fused_ok, the two launches otherwise.
+std::tuple<torch::Tensor, torch::Tensor> conv2d_pool_fwd(
+    torch::Tensor x, torch::Tensor w, c10::optional<torch::Tensor> b,
+    int64_t stride, int64_t pad,
+    c10::optional<torch::Tensor> wt_in = c10::nullopt) {
+  TORCH_CHECK(x.is_cuda() && w.is_cuda() && x.dim() == 4 && w.dim() == 4);
+  int Nb = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  int Kout = w.size(0), R = w.size(2), S = w.size(3);
+  if (is_bf16(x) ||
+      !conv_pool_fused_ok(C, H, W, Kout, R, S, (int)stride, (int)pad))
+    return maxpool2x2_fwd(conv2d_fwd(x, w, b, stride, pad, true, wt_in));
+  x = cl(x, "conv_pool_fwd.x");
+  w = w.contiguous();
+  TORCH_CHECK(w.size(1) == C && (!b || b->numel() == Kout));
+  const float* bp = b ? b->data_ptr<float>() : nullptr;
+  torch::Tensor wt;
+  if (wt_in) {
+    wt = *wt_in;
+    TORCH_CHECK(wt.is_cuda() && wt.is_contiguous() &&
+                wt.scalar_type() == torch::kFloat &&
+                wt.numel() == w.numel());
+  } else {
+    wt = StepQueue(true).wperm(w, 0);
+  }
+  int PH = (H - R + 1) / 2, PW = (W - S + 1) / 2;
+  auto pooled = empty_cl({Nb, Kout, PH, PW}, x.options());
+  auto idx = empty_cl({Nb, Kout, PH, PW}, x.options().dtype(torch::kUInt8));
+  launch_conv_pool_fwd(x.data_ptr<float>(), wt.data_ptr<float>(), bp,
+                       pooled.data_ptr<float>(), idx.data_ptr<uint8_t>(), Nb,
+                       C, H, W, Kout, R, S, stream_of(x));
+  return {pooled, idx};
 }
 
 
@@ -1645,6 +1701,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv2d_fwd", &conv2d_fwd, py::arg("x"), py::arg("w"), py::arg("b"),
         py::arg("stride"), py::arg("pad"), py::arg("relu"),
         py::arg("wt") = py::none());
+  m.def("conv2d_pool_fwd", &conv2d_pool_fwd, py::arg("x"), py::arg("w"),
+        py::arg("b"), py::arg("stride"), py::arg("pad"),
+        py::arg("wt") = py::none());
+  m.def("conv_pool_fused_ok", &conv_pool_fused_ok);
+  // -> (tile_rows, tiles, mi, lds_rows, lds_bytes)
+  m.def("conv_fwd_res_plan", [](int C, int H, int W, int OH, int OW, int R) {
+    ConvFwdResPlan p = conv_fwd_res_plan(C, H, W, OH, OW, R);
+    return std::make_tuple(p.tile_rows, p.tiles, p.mi, p.lds_rows,
+                           p.lds_bytes);
+  });
   m.def("conv2d_bwd", &conv2d_bwd);
   m.def("conv2d_bwd_into", &conv2d_bwd_into, py::arg("x"), py::arg("w"),
         py::arg("dy"), py::arg("stride"), py::arg("pad"), py::arg("need_dx"),
@@ -1700,6 +1766,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return conv_bwdw_tap_s2_ok(a, b, c, d, e, f, g, h) != 0;
   });
   m.def("pool_flatten_dropout_fwd", &pool_flatten_dropout_fwd);
+  m.def("flatten_dropout_fwd", &flatten_dropout_fwd);
   m.def("dropout_unflatten_pool_bwd_relu", &dropout_unflatten_pool_bwd_relu);
   m.def("fc_head_step", &fc_head_step, py::arg("h1"), py::arg("w"),
         py::arg("b"), py::arg("labels"), py::arg("dloss"), py::arg("p"),

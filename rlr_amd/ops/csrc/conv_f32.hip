@@ -20,6 +20,7 @@
 // wp[(r,s,ko)][c].  All reductions fixed-order; no atomics.
 #include "common.h"
 #include "launchers.h"
+#include "tail_math.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -237,13 +238,30 @@ void conv_fwd_k(const float* __restrict__ x, const float* __restrict__ wt,
 // (instead of re-gathering each patch element per K-tile — a 9x re-read
 // through L3) and A fragments are read directly with a per-pixel +1 bank
 // pad.  One image per block; B (weights) stays double-buffer streamed.
+//
+// A block owns MI*32 output pixels of one image (conv_fwd_res_plan picks
+// MI): 2x2 waves, MI row-tiles of 16 per wave.  A fragments are addressed
+// through the per-lane pixrel[mi], so the map from MFMA row to output pixel
+// is free; the K loop never sees it.
+//   POOL == false: row i of the tile is pixel p0 + i; the epilogue stores
+//       y (NHWC), bias and relu applied.
+//   POOL == true: the tile is a whole even number of output rows and row i
+//       of a 16-row MFMA tile is cell i % 4 (dy = i%4 >> 1, dx = i%4 & 1)
+//       of 2x2 window i / 4, windows in row-major pooled order.  The four
+//       accumulator registers of a lane (rows l4*4 + r) are then the four
+//       cells of ONE window: bias, relu and pool2x2_select run in registers
+//       and the epilogue stores one pooled float and one argmax byte, in
+//       the layout and coding of maxpool2x2_fwd_k.  y is never written.
+template <int MI, bool POOL>
 __global__ __launch_bounds__(256)
 void conv_fwd_res_k(const float* __restrict__ x,
                     const float* __restrict__ wt,  // [(r,s,c)][KO]
-                    const float* __restrict__ bias, float* __restrict__ y,
+                    const float* __restrict__ bias,
+                    float* __restrict__ y,         // POOL: pooled
+                    uint8_t* __restrict__ idx,     // POOL only
                     ConvShape sh, int Kdim, int relu, int ptiles,
                     int lds_rows) {
-  constexpr int BM = 128, MI = 4, NI = 2;
+  constexpr int BM = MI * 32, NI = 2;
   extern __shared__ __attribute__((aligned(16))) float dynLds[];
   float* x_lds = dynLds;                       // [lds_rows][W][C+1-padded]
   // B buffers start 16-B aligned after the (odd-strided) x region
@@ -265,6 +283,8 @@ void conv_fwd_res_k(const float* __restrict__ x,
   const int OHOW = sh.OH * sh.OW;
   const int n_blk = blockIdx.y * BN;
   const int Cp = sh.C + 1;
+  // POOL: pooled width, windows per image, first window of this tile
+  const int PW = sh.OW >> 1, PHPW = (sh.OH >> 1) * PW, w0 = p0 >> 2;
 
   const int oh_lo = p0 / sh.OW;
   // ---- load the x region once (always in-bounds: pad==0, stride==1) ----
@@ -274,24 +294,37 @@ void conv_fwd_res_k(const float* __restrict__ x,
     int total4 = lds_rows * sh.W * sh.C / 4;
     int avail_rows = sh.H - oh_lo;
     int total4_avail = min(total4, avail_rows * sh.W * sh.C / 4);
+    // (pix, c) of float4 i, carried: +1024 floats per round, no div/mod
+    int pix = (t * 4) / sh.C;
+    int c = t * 4 - pix * sh.C;
+    const int dpix = 1024 / sh.C, dc = 1024 - dpix * sh.C;
     for (int i = t; i < total4_avail; i += 256) {
       float4 q = *(const float4*)(xsrc + (long)i * 4);
-      int c = (i * 4) % sh.C;
-      int pix = (i * 4) / sh.C;
       float* dst = &x_lds[pix * Cp + c];
       dst[0] = q.x; dst[1] = q.y; dst[2] = q.z; dst[3] = q.w;
+      pix += dpix; c += dc;
+      if (c >= sh.C) { c -= sh.C; ++pix; }
     }
   }
 
-  // per-lane fragment bases: lds pixel offset of each mi's output pixel
+  // per-lane fragment bases: lds pixel offset of the output pixel that row
+  // l15 of each mi's tile stands for
   int pixrel[MI];
-  bool mval[MI];
 #pragma unroll
   for (int mi = 0; mi < MI; ++mi) {
-    int m = p0 + wr * 64 + mi * 16 + l15;
-    mval[mi] = m < OHOW;
-    int mm = mval[mi] ? m : 0;
-    int oh = mm / sh.OW, ow = mm % sh.OW;
+    int oh, ow;
+    if (POOL) {
+      int wv = w0 + (wr * MI + mi) * 4 + (l15 >> 2);
+      if (wv >= PHPW) wv = w0;  // padded row: any resident pixel
+      int ph = wv / PW, pw = wv - ph * PW;
+      oh = 2 * ph + ((l15 >> 1) & 1);
+      ow = 2 * pw + (l15 & 1);
+    } else {
+      int m = p0 + (wr * MI + mi) * 16 + l15;
+      if (m >= OHOW) m = p0;  // padded row: any resident pixel
+      oh = m / sh.OW;
+      ow = m - oh * sh.OW;
+    }
     pixrel[mi] = ((oh - oh_lo) * sh.W + ow) * Cp;
   }
 
@@ -375,14 +408,29 @@ void conv_fwd_res_k(const float* __restrict__ x,
     for (int ni = 0; ni < NI; ++ni) {
       int ko = n_blk + wc * 32 + ni * 16 + l15;
       if (ko >= sh.Kout) continue;
+      float v[4];
 #pragma unroll
       for (int r2 = 0; r2 < 4; ++r2) {
-        int m = p0 + wr * 64 + mi * 16 + l4 * 4 + r2;
-        if (m >= OHOW) continue;
-        float v = acc[mi][ni][r2];
-        if (bias) v += bias[ko];
-        if (relu) v = fmaxf(v, 0.f);
-        y[((long)nb * OHOW + m) * sh.Kout + ko] = v;
+        v[r2] = acc[mi][ni][r2];
+        if (bias) v[r2] += bias[ko];
+        if (relu) v[r2] = fmaxf(v[r2], 0.f);
+      }
+      if (POOL) {
+        int wv = w0 + (wr * MI + mi) * 4 + l4;
+        if (wv >= PHPW) continue;
+        float m;
+        uint8_t a;
+        pool2x2_select(v[0], v[1], v[2], v[3], m, a);
+        long o = ((long)nb * PHPW + wv) * sh.Kout + ko;
+        y[o] = m;
+        idx[o] = a;
+      } else {
+#pragma unroll
+        for (int r2 = 0; r2 < 4; ++r2) {
+          int m = p0 + (wr * MI + mi) * 16 + l4 * 4 + r2;
+          if (m >= OHOW) continue;
+          y[((long)nb * OHOW + m) * sh.Kout + ko] = v[r2];
+        }
       }
     }
 }
@@ -1119,6 +1167,88 @@ void conv_small_bwdw_k(const float* __restrict__ dy,
 // roles: bodies in step_roles.h, makers below, run by step_batch.hip.
 
 extern "C" {
+// ---- the resident forward's tile plan (host arithmetic only) ----
+// LDS that keeps 3 blocks on a CU (160 KiB / 3), and the launch guard
+constexpr long kResLds3 = 163840 / 3;
+constexpr long kResLdsMax = 100 * 1024;
+
+static long conv_fwd_res_lds_bytes(int lds_rows, int W, int C) {
+  long xf = ((long)lds_rows * W * (C + 1) + 3) & ~3L;
+  return (xf + 2L * BK * LDB_S) * 4;
+}
+
+ConvFwdResPlan conv_fwd_res_plan(int C, int H, int W, int OH, int OW,
+                                 int R) {
+  (void)H;
+  ConvFwdResPlan p{};
+  // a tile of whole output rows that fills its MFMA rows exactly and tiles
+  // the image exactly, the larger first: no row is issued for nothing
+  for (int mi = 6; mi >= 4; mi -= 2) {
+    int px = mi * 32;
+    if (OW <= 0 || px % OW != 0 || OH % (px / OW) != 0) continue;
+    int rows = px / OW;
+    long bytes = conv_fwd_res_lds_bytes(rows + R - 1, W, C);
+    if (bytes > kResLds3) continue;
+    p.tile_rows = rows;
+    p.tiles = OH / rows;
+    p.mi = mi;
+    p.lds_rows = rows + R - 1;
+    p.lds_bytes = bytes;
+    return p;
+  }
+  // otherwise 128 pixels wherever they fall: the last tile is padded, and
+  // the region spans the rows a tile can straddle (tile_rows = 0: not whole)
+  p.tile_rows = 0;
+  p.tiles = (OH * OW + 127) / 128;
+  p.mi = 4;
+  p.lds_rows = (127 / OW) + 2 + R - 1;
+  p.lds_bytes = conv_fwd_res_lds_bytes(p.lds_rows, W, C);
+  return p;
+}
+
+// launch_conv_fwd's condition for the resident kernel
+static bool conv_fwd_resident(int C, int H, int W, int OH, int OW, int R,
+                              int S, int stride, int pad) {
+  (void)S;
+  return pad == 0 && stride == 1 && (C % 32) == 0 && OH * OW >= 128 &&
+         conv_fwd_res_plan(C, H, W, OH, OW, R).lds_bytes <= kResLdsMax;
+}
+
+int conv_pool_fused_ok(int C, int H, int W, int Kout, int R, int S,
+                       int stride, int pad) {
+  if (stride != 1 || pad != 0 || H < R || W < S) return 0;
+  int OH = H - R + 1, OW = W - S + 1;
+  int small = C * R * S <= 32 && (Kout == 32 || Kout == 64);
+  if (small || !conv_fwd_resident(C, H, W, OH, OW, R, S, stride, pad))
+    return 0;
+  int rows = conv_fwd_res_plan(C, H, W, OH, OW, R).tile_rows;
+  return (OH % 2) == 0 && (OW % 2) == 0 && rows > 0 && (rows % 2) == 0;
+}
+
+// idx != nullptr: the pooled epilogue (y = pooled); needs
+// conv_pool_fused_ok, which makes every tile whole windows
+static void launch_conv_fwd_res(const float* x, const float* wt,
+                                const float* bias, float* y, uint8_t* idx,
+                                const ConvShape& sh, int relu,
+                                hipStream_t st) {
+  ConvFwdResPlan p = conv_fwd_res_plan(sh.C, sh.H, sh.W, sh.OH, sh.OW, sh.R);
+  int Kdim = sh.C * sh.R * sh.S;
+  dim3 g((long)sh.Nb * p.tiles, (sh.Kout + BN - 1) / BN, 1);
+#define RLR_RES(MI, POOL)                                                  \
+  conv_fwd_res_k<MI, POOL><<<g, 256, p.lds_bytes, st>>>(                   \
+      x, wt, bias, y, idx, sh, Kdim, relu, p.tiles, p.lds_rows)
+  if (p.mi == 6) { if (idx) RLR_RES(6, true); else RLR_RES(6, false); }
+  else           { if (idx) RLR_RES(4, true); else RLR_RES(4, false); }
+#undef RLR_RES
+}
+
+void launch_conv_pool_fwd(const float* x, const float* wt, const float* bias,
+                          float* pooled, uint8_t* idx, int Nb, int C, int H,
+                          int W, int Kout, int R, int S, void* s) {
+  ConvShape sh{Nb, C, H, W, Kout, R, S, H - R + 1, W - S + 1, 1, 0};
+  launch_conv_fwd_res(x, wt, bias, pooled, idx, sh, 1, (hipStream_t)s);
+}
+
 void launch_conv_fwd(const float* x, const float* wt, const float* bias,
                      float* y, int Nb, int C, int H, int W, int Kout, int R,
                      int S, int OH, int OW, int stride, int pad, int relu,
@@ -1138,19 +1268,9 @@ void launch_conv_fwd(const float* x, const float* wt, const float* bias,
     return;
   }
   bool v4 = (C % 32) == 0;
-  if (pad == 0 && stride == 1 && v4 && OH * OW >= 128) {
-    // x-resident fast path: LDS = x region + 2 B buffers
-    int ptiles = (OH * OW + 127) / 128;
-    int oh_span = (127 / OW) + 2;               // output rows per tile (+1)
-    int lds_rows = oh_span + R - 1;
-    long xf = ((long)lds_rows * W * (C + 1) + 3) & ~3L;
-    long lds_bytes = (xf + 2L * BK * LDB_S) * 4;
-    if (lds_bytes <= 100 * 1024) {
-      dim3 g2((long)Nb * ptiles, (Kout + BN - 1) / BN, 1);
-      conv_fwd_res_k<<<g2, 256, lds_bytes, st>>>(x, wt, bias, y, sh, Kdim,
-                                                 relu, ptiles, lds_rows);
-      return;
-    }
+  if (conv_fwd_resident(C, H, W, OH, OW, R, S, stride, pad)) {
+    launch_conv_fwd_res(x, wt, bias, y, nullptr, sh, relu, st);
+    return;
   }
   if (pad == 0 && v4)
     conv_fwd_k<true, true><<<grid, 256, 0, st>>>(x, wt, bias, y, sh, Kdim,

@@ -53,6 +53,9 @@ __device__ __forceinline__ int seam_tile_addr(int c0, int hw0, int e,
   return hw * S + c;
 }
 
+// POOLED_IN: x is already the pooled image (conv_fwd_res_k's pooled
+// epilogue wrote it, and idx): the first phase only copies it into the tile.
+template <bool POOLED_IN>
 __global__ __launch_bounds__(kSeamBlock)
 void pool_flatten_dropout_fwd_k(const float* __restrict__ x,
                                 float* __restrict__ pooled,
@@ -75,20 +78,24 @@ void pool_flatten_dropout_fwd_k(const float* __restrict__ x,
   for (int it = threadIdx.x; it < n4; it += kSeamBlock) {
     int ohw = it / c4n;
     int c = (it - ohw * c4n) * 4;
-    int oh = ohw / OW, ow = ohw - oh * OW;
-    const float* p0 = xb + ((long)(2 * oh) * W + 2 * ow) * C + c;
-    float4 v00 = *(const float4*)p0;
-    float4 v01 = *(const float4*)(p0 + C);
-    float4 v10 = *(const float4*)(p0 + WC);
-    float4 v11 = *(const float4*)(p0 + WC + C);
     float4 m;
-    uchar4 a;
-    pool2x2_select(v00.x, v01.x, v10.x, v11.x, m.x, a.x);
-    pool2x2_select(v00.y, v01.y, v10.y, v11.y, m.y, a.y);
-    pool2x2_select(v00.z, v01.z, v10.z, v11.z, m.z, a.z);
-    pool2x2_select(v00.w, v01.w, v10.w, v11.w, m.w, a.w);
-    *(float4*)(pooled + ob + (long)it * 4) = m;
-    *(uchar4*)(idx + ob + (long)it * 4) = a;
+    if (POOLED_IN) {
+      m = *(const float4*)(x + ob + (long)it * 4);
+    } else {
+      int oh = ohw / OW, ow = ohw - oh * OW;
+      const float* p0 = xb + ((long)(2 * oh) * W + 2 * ow) * C + c;
+      float4 v00 = *(const float4*)p0;
+      float4 v01 = *(const float4*)(p0 + C);
+      float4 v10 = *(const float4*)(p0 + WC);
+      float4 v11 = *(const float4*)(p0 + WC + C);
+      uchar4 a;
+      pool2x2_select(v00.x, v01.x, v10.x, v11.x, m.x, a.x);
+      pool2x2_select(v00.y, v01.y, v10.y, v11.y, m.y, a.y);
+      pool2x2_select(v00.z, v01.z, v10.z, v11.z, m.z, a.z);
+      pool2x2_select(v00.w, v01.w, v10.w, v11.w, m.w, a.w);
+      *(float4*)(pooled + ob + (long)it * 4) = m;
+      *(uchar4*)(idx + ob + (long)it * 4) = a;
+    }
     float* t = tile + ohw * S + c;
     t[0] = m.x; t[1] = m.y; t[2] = m.z; t[3] = m.w;
   }
@@ -318,8 +325,20 @@ void launch_pool_flatten_dropout_fwd(const float* x, float* pooled,
                                      const unsigned long long* state,
                                      int site, void* s) {
   if (B <= 0) return;
-  pool_flatten_dropout_fwd_k<<<(unsigned)B, kSeamBlock, 0, (hipStream_t)s>>>(
-      x, pooled, idx, d, mask, H, W, H / 2, W / 2, C, p, state, site);
+  pool_flatten_dropout_fwd_k<false>
+      <<<(unsigned)B, kSeamBlock, 0, (hipStream_t)s>>>(
+          x, pooled, idx, d, mask, H, W, H / 2, W / 2, C, p, state, site);
+}
+
+void launch_flatten_dropout_fwd(const float* pooled, float* d, uint8_t* mask,
+                                long B, int OH, int OW, int C, float p,
+                                const unsigned long long* state, int site,
+                                void* s) {
+  if (B <= 0) return;
+  pool_flatten_dropout_fwd_k<true>
+      <<<(unsigned)B, kSeamBlock, 0, (hipStream_t)s>>>(
+          pooled, nullptr, nullptr, d, mask, 2 * OH, 2 * OW, OH, OW, C, p,
+          state, site);
 }
 
 void launch_dropout_unflatten_pool_bwd_relu(const float* g,

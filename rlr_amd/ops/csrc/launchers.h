@@ -78,6 +78,15 @@ struct StepRole {
 static_assert(sizeof(StepRole) <= 104, "16 of them are kernel arguments");
 constexpr int kStepMaxRoles = 16;
 
+// How the x-resident fp32 conv forward cuts one image: `tiles` blocks of
+// mi * 32 output pixels (mi MFMA row-tiles per wave), each holding lds_rows
+// input rows in lds_bytes of LDS.  tile_rows is the tile in output rows, 0
+// where it is not a whole number of them.
+struct ConvFwdResPlan {
+  int tile_rows, tiles, mi, lds_rows;
+  long lds_bytes;
+};
+
 extern "C" {
 // step_batch.hip.  launch_step_role runs one role now, launch_step_batch up
 // to kStepMaxRoles in one launch; both skip roles with count == 0 and return
@@ -184,6 +193,13 @@ void launch_pool_flatten_dropout_fwd(const float* x, float* pooled,
                                      long B, int H, int W, int C, float p,
                                      const unsigned long long* state,
                                      int site, void* s);
+// the same kernel from an already pooled image (B,OH,OW,C), as
+// launch_conv_pool_fwd leaves it: writes d / mask only; needs
+// pool_seam_fused_ok(C, 2 * OH, 2 * OW)
+void launch_flatten_dropout_fwd(const float* pooled, float* d, uint8_t* mask,
+                                long B, int OH, int OW, int C, float p,
+                                const unsigned long long* state, int site,
+                                void* s);
 void launch_dropout_unflatten_pool_bwd_relu(const float* g,
                                             const uint8_t* mask,
                                             const uint8_t* idx,
@@ -323,6 +339,21 @@ void launch_conv_fwd(const float* x, const float* wt, const float* bias,
                      float* y, int Nb, int C, int H, int W, int Kout, int R,
                      int S, int OH, int OW, int stride, int pad, int relu,
                      void* s);
+// The resident forward's tile plan (host only, a pure function of the
+// shape): a tile of whole output rows with no padded MFMA row, 192 pixels
+// at most, where one exists within the LDS that keeps 3 blocks on a CU;
+// 128 pixels wherever they fall otherwise.
+ConvFwdResPlan conv_fwd_res_plan(int C, int H, int W, int OH, int OW, int R);
+// conv + bias + relu + maxpool2x2 in the resident forward's epilogue:
+// pooled / idx (Nb, OH/2, OW/2, Kout) NHWC as launch_maxpool2x2_fwd writes
+// them; the conv output itself is never stored.  conv_pool_fused_ok: the
+// resident path applies, OH and OW are even and the planned tile is a whole
+// even number of output rows.
+int conv_pool_fused_ok(int C, int H, int W, int Kout, int R, int S,
+                       int stride, int pad);
+void launch_conv_pool_fwd(const float* x, const float* wt, const float* bias,
+                          float* pooled, uint8_t* idx, int Nb, int C, int H,
+                          int W, int Kout, int R, int S, void* s);
 void launch_conv_bwd_data_relu(const float* dy, const float* wp,
                                float* dx, const float* relu_y, int Nb,
                                int C, int H, int W, int Kout, int R, int S,
