@@ -100,6 +100,42 @@ Rules (each a HIP kernel on the GPU path, ops/csrc/aggregation.hip):
     --server_clip runs in front unchanged; BatchNorm buffers take the
     unweighted mean over the theta selected agents.  Non-finite updates are
     out of scope.
+  * FoolsGold (build addition, --aggr foolsgold; Fung, Yoon, Beschastnikh,
+    "The Limitations of Federated Learning in Sybil Settings", RAID 2020):
+    the one rule with server state across rounds.  H (num_agents, n) fp64
+    on the updates' device, zeros before the first round, holds every
+    agent's summed updates; kappa = --foolsgold_kappa > 0; ids[0..K) the
+    sampled agents, distinct.  Per round:
+        0. H[ids[k]] += C[k]  for every k          one fp64 add per element
+        1. G[i][j] = sum_t H[ids[i]][t] * H[ids[j]][t]   exactly symmetric
+        2. den = sqrt(G[i][i] * G[j][j])
+           cs[i][j] = den > 0 ? G[i][j] / den : 0  for i != j; cs[i][i] = 0
+        3. v[i] = max_j cs[i][j]          the zero diagonal takes part
+        4. for i != j: if v[i] < v[j]: cs[i][j] = (cs[i][j] * v[i]) / v[j]
+           (pardoning; v is NOT recomputed)
+        5. wv[i] = clamp(1 - max_j cs[i][j], 0, 1)   diagonal 0 again
+        6. m = max_i wv[i]; if m > 0: wv[i] = wv[i] / m
+           if wv[i] == 1.0: wv[i] = 0.99
+        7. alpha[i] = clamp(kappa * (ln(wv[i] / (1 - wv[i])) + 0.5), 0, 1)
+           (wv = 0 gives -inf, which clamps to 0)
+        8. aggregate = (sum_k alpha[k] * C[k]) * (1.0 / K), sequential in
+           sampled order from 0
+    Steps 2-7 are foolsgold_weights() below, THE CPU rule.  The divisor is
+    K, not sum(alpha): the rule scales each agent's learning rate, so with
+    no sybils it is the unweighted mean and a round of all-sybil agents
+    moves nothing (m == 0 leaves wv, alpha and the model where they are).
+    Unweighted by data size like every other build addition.  On the GPU
+    (K <= 512) step 0 is rows_add_k and steps 2-7 three small launches
+    (ops/csrc/foolsgold.hip), step 1 the fp64 MFMA Gram stages of
+    pairdist.hip over the sampled rows of H, step 8 the fused avg kernel
+    with w = alpha and divisor K; no host sync.  The RLR vote is over ALL
+    K, noise behaves as for avg on each backend, --server_clip runs in
+    front so H accumulates the clipped rows, BatchNorm buffer deltas take
+    (sum_k alpha[k] delta[k]) * (1 / K).  H is a pure function of the
+    updates and bitwise equal between backends; G, and so alpha, agree to
+    rounding (bounds in PARITY.md).  last_weights holds the raw alpha, not
+    normalised (its sum may be 0); state_dict() carries H into the
+    checkpoint.  Non-finite updates are out of scope.
   * sign (aggregation.py:71-75): sign(sum_k sign(U_k)).
   * server-side norm clipping (build addition, --server_clip > 0; Sun et
     al., "Can You Really Backdoor Federated Learning?", and the clipping
@@ -134,7 +170,7 @@ import torch
 from torch.nn import functional as F
 
 from .ops import ext, force_eager
-from .options import check_geomed, check_server_clip
+from .options import check_foolsgold, check_geomed, check_server_clip
 from .utils.rng import derive_seed, torch_gen
 
 
@@ -182,6 +218,28 @@ def bulyan_window_mean(rows, beta):
     return out * (1.0 / beta)
 
 
+def foolsgold_weights(G, kappa):
+    """Steps 2-7 of FoolsGold in plain torch — THE CPU rule (module
+    docstring) and the reference for the kernel: (alpha, cs) from the Gram
+    matrix G (K, K) of the sampled history rows, cs the cosine matrix of
+    step 2, before pardoning.  No host sync."""
+    g = G.diagonal()
+    den = torch.sqrt(g.unsqueeze(1) * g.unsqueeze(0))
+    zero = torch.zeros_like(G)
+    cs = torch.where(den > 0, G / den, zero)
+    cs.fill_diagonal_(0.0)
+    v = cs.max(dim=1).values
+    vi, vj = v.unsqueeze(1), v.unsqueeze(0)
+    # never on the diagonal: v[i] < v[i] is false
+    pardoned = torch.where(vi < vj, (cs * vi) / vj, cs)
+    wv = (1.0 - pardoned.max(dim=1).values).clamp(0.0, 1.0)
+    m = wv.max()
+    wv = torch.where(m > 0, wv / m, wv)
+    wv = torch.where(wv == 1.0, torch.full_like(wv, 0.99), wv)
+    alpha = (kappa * (torch.log(wv / (1.0 - wv)) + 0.5)).clamp(0.0, 1.0)
+    return alpha, cs
+
+
 class Aggregation:
     def __init__(self, agent_data_sizes, n_params, poisoned_val_loader,
                  args, writer=None):
@@ -194,7 +252,11 @@ class Aggregation:
         self.cum_net_mov = 0.0
         # krum, bulyan: sampled positions kept last round
         self.last_selected = None
-        self.last_weights = None    # geomed: final weights, normalised
+        # geomed: final weights, normalised; foolsgold: the raw alpha
+        self.last_weights = None
+        # foolsgold: (num_agents, n) fp64 summed updates per agent, on the
+        # updates' device; None until the first round
+        self.foolsgold_history = None
         # server_clip: last round's factors s (K), bound tau (0-d) and
         # pre-clip norms (K), on the updates' device
         self.last_clip_scale = None
@@ -221,7 +283,8 @@ class Aggregation:
             stacked = self.server_clip_updates(stacked)
             self._log_clip(agent_ids, cur_round)
 
-        rule, w, span, subset = self._resolve(stacked, agent_ids, cur_round)
+        rule, w, span, subset, divisor = self._resolve(stacked, agent_ids,
+                                                       cur_round)
         K = stacked.shape[0]
         rlr = self.args.robustLR_threshold > 0
 
@@ -234,7 +297,8 @@ class Aggregation:
             ext().fused_avg_rlr_apply(
                 stacked, w, global_model.flat_params, rlr,
                 float(self.args.robustLR_threshold), float(self.server_lr),
-                float(noise_std), seed, 0, False)
+                float(noise_std), seed, 0, False,
+                0.0 if divisor is None else float(divisor))
             return
 
         if (_gpu(stacked) and span is not None and self.args.noise == 0
@@ -272,40 +336,48 @@ class Aggregation:
 
     def _resolve(self, stacked, agent_ids, cur_round):
         """What --aggr decides for this round, looked at in this one place:
-        (rule, weights, span, subset).  weights: for a weighted mean of the
-        rows; span: [lo, hi) of each sorted column to average; subset:
-        (selected positions, theta, beta) for bulyan's trimmed mean around
-        the median of the selected rows; none of them for sign.
+        (rule, weights, span, subset, divisor).  weights: for a weighted
+        mean of the rows, divided by divisor (None: by their sum); span:
+        [lo, hi) of each sorted column to average; subset: (selected
+        positions, theta, beta) for bulyan's trimmed mean around the median
+        of the selected rows; none of them for sign.
         rule(stacked) is the aggregate as the composed path computes it.
         Sets last_selected / last_weights and logs what the rule chose."""
         aggr, K, dev = self.args.aggr, stacked.shape[0], stacked.device
         if aggr == 'avg':
             w = self._weights(agent_ids, dev)
-            return (lambda U: self._mean(U, w, self._avg_mean)), w, None, None
+            return ((lambda U: self._mean(U, w, self._avg_mean)), w, None,
+                    None, None)
         if aggr == 'krum':
             self.last_selected = self.krum_select(stacked)
             self._log_krum(agent_ids, cur_round)
             w = self._krum_weights(K, dev)
             return ((lambda U: self._mean(U, w, self._krum_mean)), w, None,
-                    None)
+                    None, None)
         if aggr == 'geomed':
             a = self.geomed_weights(stacked)
             self.last_weights = a / a.sum()
             self._log_geomed(agent_ids, cur_round)
             return ((lambda U: self._mean(U, a, self._geomed_mean)), a, None,
-                    None)
+                    None, None)
+        if aggr == 'foolsgold':
+            alpha = self.last_weights = self.foolsgold_alpha(stacked,
+                                                             agent_ids)
+            self._log_foolsgold(agent_ids, cur_round)
+            return ((lambda U: self._foolsgold_mean(U, alpha)), alpha, None,
+                    None, K)
         if aggr == 'bulyan':
             theta, beta = self._bulyan_counts(K)
             sel = self.last_selected = self.bulyan_select(stacked)
             self._log_bulyan(agent_ids, cur_round)
             return ((lambda U: self._bulyan_trim(U, sel)), None, None,
-                    (sel, theta, beta))
+                    (sel, theta, beta), None)
         if aggr == 'comed':
-            return self.agg_comed, None, self._comed_span(K), None
+            return self.agg_comed, None, self._comed_span(K), None, None
         if aggr == 'trmean':
-            return self.agg_trmean, None, self._trim_span(K), None
+            return self.agg_trmean, None, self._trim_span(K), None, None
         if aggr == 'sign':
-            return self.agg_sign, None, None, None
+            return self.agg_sign, None, None, None, None
         raise ValueError(aggr)
 
     # ------------------------------------------------------- server clip
@@ -627,6 +699,130 @@ class Aggregation:
             share = float(self.last_weights[bad].sum()) if bad else 0.0
             self.writer.add_scalar('Geomed/Corrupt_Weight', share, cur_round)
 
+    # --------------------------------------------------------- foolsgold
+
+    def _foolsgold_ids(self, agent_ids):
+        """The sampled ids as a CPU int64 vector, checked: distinct and
+        below num_agents."""
+        ids = [int(i) for i in agent_ids]
+        A = int(self.args.num_agents)
+        if any(i < 0 or i >= A for i in ids):
+            raise ValueError(
+                f"foolsgold: agent ids must be in [0, num_agents) = "
+                f"[0, {A}), got {ids}")
+        if len(set(ids)) != len(ids):
+            raise ValueError(
+                f"foolsgold: agent ids must be distinct, got {ids}")
+        return torch.tensor(ids, dtype=torch.long)
+
+    @staticmethod
+    def _foolsgold_kernel(t, K):
+        return _gpu(t) and K <= ext().foolsgold_max_k()
+
+    def foolsgold_accumulate(self, stacked, agent_ids):
+        """Step 0: H[ids[k]] += stacked[k].  H is allocated, as zeros on
+        stacked's device, by the first call."""
+        idx = self._foolsgold_ids(agent_ids)
+        K, n = stacked.shape
+        if len(idx) != K:
+            raise ValueError(
+                f"foolsgold: {len(idx)} agent ids for {K} updates")
+        H = self.foolsgold_history
+        if H is None:
+            H = self.foolsgold_history = torch.zeros(
+                int(self.args.num_agents), n, dtype=torch.float64,
+                device=stacked.device)
+        if H.shape[1] != n or H.device != stacked.device:
+            raise ValueError(
+                f"foolsgold: the history is {tuple(H.shape)} on {H.device}, "
+                f"the updates are {tuple(stacked.shape)} on {stacked.device}")
+        if self._foolsgold_kernel(stacked, K):
+            ext().rows_add_(H, idx, stacked.contiguous())
+        else:
+            H.index_add_(0, idx.to(H.device), stacked)
+
+    def foolsgold_gram(self, agent_ids):
+        """Step 1: the (K, K) Gram matrix of the sampled history rows,
+        exactly symmetric."""
+        idx = self._foolsgold_ids(agent_ids)
+        H, K = self.foolsgold_history, len(idx)
+        if self._foolsgold_kernel(H, K):
+            return ext().gram_rows(H, idx)
+        Hs = H[idx.to(H.device)]
+        if _gpu(H):
+            # above the kernel's K limit: one triangle mirrored, so G is
+            # symmetric whatever the BLAS does
+            G = Hs @ Hs.T
+        else:
+            G = torch.empty(K, K, dtype=torch.float64, device=H.device)
+            for i in range(K):
+                G[i] = (Hs * Hs[i]).sum(1)
+        up = torch.triu(G, diagonal=1)
+        return up + up.T + torch.diag(G.diagonal())
+
+    def foolsgold_alpha(self, stacked, agent_ids):
+        """Steps 0-7: adds this round to the history and returns the raw
+        alpha (K) of the sampled agents.  One call is one round."""
+        kappa = float(self.args.foolsgold_kappa)
+        check_foolsgold(kappa)
+        self.foolsgold_accumulate(stacked, agent_ids)
+        G = self.foolsgold_gram(agent_ids)
+        if self._foolsgold_kernel(G, G.shape[0]):
+            return ext().foolsgold_weights(G, kappa)[0]
+        # the CPU rule; above the kernel's K limit the same on the device
+        return foolsgold_weights(G, kappa)[0]
+
+    @staticmethod
+    def _foolsgold_mean(stacked, alpha):
+        """(sum_k alpha[k] U[k]) * (1 / K), the sum sequential from 0."""
+        K = stacked.shape[0]
+        if _gpu(stacked):
+            return ext().agg_avg(stacked, alpha, float(K))
+        return _row_sum(stacked, alpha) * (1.0 / K)
+
+    def agg_foolsgold(self, stacked, agent_ids):
+        """FoolsGold aggregate of the updates (module docstring), fp64; one
+        call is one round of the history.  Remembers the raw alpha in
+        last_weights."""
+        self.last_weights = self.foolsgold_alpha(stacked, agent_ids)
+        return self._foolsgold_mean(stacked, self.last_weights)
+
+    def _log_foolsgold(self, agent_ids, cur_round):
+        """The one place that syncs for logging."""
+        if self.writer:
+            a = self.last_weights.cpu()
+            bad = [p for p, i in enumerate(agent_ids)
+                   if i < self.args.num_corrupt]
+            good = [p for p, i in enumerate(agent_ids)
+                    if i >= self.args.num_corrupt]
+            if bad:
+                self.writer.add_scalar('FoolsGold/Corrupt_Alpha_Mean',
+                                       float(a[bad].mean()), cur_round)
+            if good:
+                self.writer.add_scalar('FoolsGold/Honest_Alpha_Mean',
+                                       float(a[good].mean()), cur_round)
+
+    def state_dict(self):
+        """The server state a checkpoint has to carry: the FoolsGold
+        history once it exists, nothing for every other rule."""
+        if (self.args.aggr == 'foolsgold'
+                and self.foolsgold_history is not None):
+            return {'foolsgold_history': self.foolsgold_history}
+        return {}
+
+    def load_state_dict(self, state, device=None):
+        """Restores what state_dict() returned, onto `device` (default:
+        where the saved tensor lives)."""
+        H = state.get('foolsgold_history')
+        if H is None:
+            return
+        want = (int(self.args.num_agents), self.n_params)
+        if tuple(H.shape) != want or H.dtype != torch.float64:
+            raise ValueError(
+                f"foolsgold history is {tuple(H.shape)} {H.dtype}; this run "
+                f"needs {want} torch.float64")
+        self.foolsgold_history = H.to(device or H.device).clone()
+
     def agg_sign(self, stacked):
         if _gpu(stacked):
             return ext().agg_sign(stacked)
@@ -668,14 +864,20 @@ class Aggregation:
         nothing about them."""
         if self.args.aggr in ('krum', 'bulyan'):
             return self._krum_weights(len(agent_ids), device)
-        if self.args.aggr == 'geomed':
+        if self.args.aggr in ('geomed', 'foolsgold'):
             return self.last_weights.to(device)
         return self._weights(agent_ids, device)
+
+    def _buffer_divisor(self, K):
+        """What the weighted mean of the buffers divides by: None for the
+        sum of the weights, K under foolsgold, as for the parameters."""
+        return K if self.args.aggr == 'foolsgold' else None
 
     def aggregate_buffers(self, global_model, buffer_deltas, agent_ids):
         """FedAvg-BN: data-weighted mean of BatchNorm running-stat deltas
         (build extension — the reference has no BN).  Under krum and bulyan:
-        the unweighted mean over the agents selected for the parameters.  Under
+        the unweighted mean over the agents selected for the parameters;
+        under foolsgold (sum_k alpha[k] delta[k]) * (1 / K).  Under
         --server_clip agent k's delta is first multiplied by the s[k] its
         update was clipped with."""
         if global_model.n_buffers == 0 or buffer_deltas is None:
@@ -691,14 +893,19 @@ class Aggregation:
             # an agent's buffer delta shrinks with its update
             buffer_deltas = (buffer_deltas.double()
                              * self.last_clip_scale.to(dev).unsqueeze(1))
+        div = self._buffer_divisor(buffer_deltas.shape[0])
         if _gpu(buffer_deltas):
             # same weighted-mean HIP kernel as the parameter path (the
             # buffer matrix is tiny — K x ~10k — so the fp64 round-trip
             # is free and keeps one aggregation code path)
-            mean = ext().agg_avg(buffer_deltas.double().contiguous(), w)
-        else:
+            mean = ext().agg_avg(buffer_deltas.double().contiguous(), w,
+                                 0.0 if div is None else float(div))
+        elif div is None:
             mean = (buffer_deltas.double()
                     * (w / w.sum()).unsqueeze(1)).sum(dim=0)
+        else:
+            mean = ((buffer_deltas.double() * w.unsqueeze(1)).sum(dim=0)
+                    * (1.0 / div))
         global_model.flat_buffers.add_(mean.to(global_model.flat_buffers.dtype))
 
     # ------------------------------------------------- server-side extras

@@ -204,6 +204,14 @@ def run(args, writer=None, progress=False):
         state = load_checkpoint(args.resume, gm, expect_args=args)
         start_round = state['round']
         cum_poison_acc_mean = state['cum_poison_acc_mean']
+        # the server's own state across rounds, on every rank
+        if args.aggr == 'foolsgold':
+            if 'foolsgold_history' not in state.get('server_state', {}):
+                raise ValueError(
+                    f"checkpoint {args.resume!r} holds no FoolsGold history "
+                    f"— it was not written by an --aggr foolsgold run")
+            aggregator.load_state_dict(state['server_state'],
+                                       device=gm.device)
 
     history = {'round': [], 'val_acc': [], 'val_loss': [], 'poison_acc': [],
                'poison_loss': [], 'rounds_per_sec': []}
@@ -263,7 +271,8 @@ def run(args, writer=None, progress=False):
                     os.makedirs(args.ckpt_dir, exist_ok=True)
                     save_checkpoint(
                         os.path.join(args.ckpt_dir, f'round_{rnd:06d}.pt'),
-                        gm, rnd, args, cum_poison_acc_mean)
+                        gm, rnd, args, cum_poison_acc_mean,
+                        server_state=aggregator.state_dict())
 
     if rank == 0:
         print('Training has finished!')

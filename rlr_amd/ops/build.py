@@ -24,7 +24,7 @@ KERNEL_SOURCES = [
     'elementwise.hip', 'flatopt.hip', 'aggregation.hip', 'gemm_f32.hip',
     'gemm_bf16.hip', 'conv_f32.hip', 'conv_bf16.hip', 'conv_bwdw_tap.hip', 'batchnorm.hip',
     'poison.hip', 'orderstat.hip', 'pairdist.hip', 'geomed.hip',
-    'fused_tail.hip', 'step_batch.hip', 'rowclip.hip',
+    'fused_tail.hip', 'step_batch.hip', 'rowclip.hip', 'foolsgold.hip',
 ]
 BINDINGS = 'bindings.cpp'
 

@@ -631,17 +631,26 @@ static torch::Tensor lr_buf(bool want_lr, long n, const torch::Tensor& U) {
   return torch::empty({want_lr ? n : 0}, U.options());
 }
 
+// What a weighted mean divides by: the caller's divisor when it gives one
+// (> 0), which needs no host read; sum(w), read back from the device, for
+// the default 0.
+static double mean_divisor(const torch::Tensor& w, double divisor) {
+  CHK(divisor >= 0.0);
+  return divisor > 0.0 ? divisor : w.sum().item<double>();
+}
+
 torch::Tensor fused_avg_rlr_apply(torch::Tensor U, torch::Tensor w,
                                   torch::Tensor params, bool rlr,
                                   double thresh, double slr,
                                   double noise_std, int64_t seed,
-                                  int64_t offset, bool want_lr) {
+                                  int64_t offset, bool want_lr,
+                                  double divisor) {
   check_matrix(U, INT32_MAX);
   check_vector(w, U, U.size(0));
   check_vector(params, U, U.size(1), torch::kFloat32);
   int K = U.size(0);
   long n = U.size(1);
-  double wsum = w.sum().item<double>();
+  double wsum = mean_divisor(w, divisor);
   auto lr = lr_buf(want_lr, n, U);
   launch_fused_avg_rlr_apply(
       U.data_ptr<double>(), w.data_ptr<double>(), K, n, 1.0 / wsum,
@@ -661,12 +670,12 @@ torch::Tensor rlr_vote(torch::Tensor U, double thresh, double slr) {
   return lr;
 }
 
-torch::Tensor agg_avg(torch::Tensor U, torch::Tensor w) {
+torch::Tensor agg_avg(torch::Tensor U, torch::Tensor w, double divisor) {
   check_matrix(U, INT32_MAX);
   check_vector(w, U, U.size(0));
   int K = U.size(0);
   long n = U.size(1);
-  double wsum = w.sum().item<double>();
+  double wsum = mean_divisor(w, divisor);
   auto out = torch::empty({n}, U.options());
   launch_agg_avg(U.data_ptr<double>(), w.data_ptr<double>(), K, n,
                  1.0 / wsum, out.data_ptr<double>(), stream_of(U));
@@ -773,6 +782,72 @@ torch::Tensor pairwise_sqdist(torch::Tensor U) {
   launch_pairwise_sqdist(U.data_ptr<double>(), K, n, ws.data_ptr<double>(),
                          D.data_ptr<double>(), stream_of(U));
   return D;
+}
+
+// idx: K row indices of H as a CPU int64 vector.  Checked HERE, on the host,
+// to be in range and distinct, and only then uploaded: the kernels
+// dereference the device copy as given.
+static torch::Tensor upload_rows(const torch::Tensor& H,
+                                 const torch::Tensor& idx, int64_t max_k) {
+  CHK(H.is_cuda());
+  CHK(H.dim() == 2);
+  CHK(H.scalar_type() == torch::kFloat64);
+  CHK(H.is_contiguous());
+  CHK(H.size(0) >= 1 && H.size(1) >= 1);
+  CHK(!idx.is_cuda());
+  CHK(idx.scalar_type() == torch::kInt64);
+  CHK(idx.dim() == 1 && idx.is_contiguous());
+  const int64_t K = idx.numel();
+  CHK(K >= 1 && K <= max_k && K <= H.size(0));
+  const int64_t* p = idx.data_ptr<int64_t>();
+  std::vector<char> seen(H.size(0), 0);
+  for (int64_t k = 0; k < K; ++k) {
+    TORCH_CHECK(p[k] >= 0 && p[k] < H.size(0), "row index ", p[k],
+                " is outside [0, ", H.size(0), ")");
+    TORCH_CHECK(!seen[p[k]], "row index ", p[k], " appears twice");
+    seen[p[k]] = 1;
+  }
+  return idx.to(H.device());
+}
+
+// H[idx[k]] += U[k] in place, for distinct rows idx of the (A, n) history
+void rows_add_(torch::Tensor H, torch::Tensor idx, torch::Tensor U) {
+  auto rows = upload_rows(H, idx, INT32_MAX);
+  check_matrix(U, INT32_MAX);
+  CHK(U.device() == H.device());
+  CHK(U.size(0) == idx.numel() && U.size(1) == H.size(1));
+  launch_rows_add(H.data_ptr<double>(), (const long*)rows.data_ptr<int64_t>(),
+                  U.data_ptr<double>(), (int)U.size(0), U.size(1),
+                  stream_of(H));
+}
+
+// G (K, K) = Gram matrix of the rows idx of H, exactly symmetric
+torch::Tensor gram_rows(torch::Tensor H, torch::Tensor idx) {
+  auto rows = upload_rows(H, idx, pairdist_max_k());
+  int K = idx.numel();
+  long n = H.size(1);
+  auto ws = torch::empty({pairdist_ws_doubles(K, n)}, H.options());
+  auto G = torch::empty({K, K}, H.options());
+  launch_gram_rows(H.data_ptr<double>(), (const long*)rows.data_ptr<int64_t>(),
+                   K, n, ws.data_ptr<double>(), G.data_ptr<double>(),
+                   stream_of(H));
+  return G;
+}
+
+// FoolsGold's (alpha, cs) from the Gram matrix of the sampled history rows:
+// cs the cosine matrix before pardoning, alpha the weights in [0, 1]
+std::tuple<torch::Tensor, torch::Tensor> foolsgold_weights(torch::Tensor G,
+                                                           double kappa) {
+  check_matrix(G, foolsgold_max_k());
+  CHK(G.size(0) == G.size(1));
+  CHK(kappa > 0.0);
+  int K = G.size(0);
+  auto cs = torch::empty({K, K}, G.options());
+  auto alpha = torch::empty({K}, G.options());
+  launch_foolsgold_weights(G.data_ptr<double>(), K, kappa,
+                           cs.data_ptr<double>(), alpha.data_ptr<double>(),
+                           stream_of(G));
+  return {alpha, cs};
 }
 
 // d2[k] = ||U_k - z||^2, z the weighted mean of the rows under a (K fp64)
@@ -1665,9 +1740,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pgd_project", &pgd_project);
   m.def("delta64", &delta64);
   m.def("gather_grads", &gather_grads);
-  m.def("fused_avg_rlr_apply", &fused_avg_rlr_apply);
+  m.def("fused_avg_rlr_apply", &fused_avg_rlr_apply, py::arg("U"),
+        py::arg("w"), py::arg("params"), py::arg("rlr"), py::arg("thresh"),
+        py::arg("slr"), py::arg("noise_std"), py::arg("seed"),
+        py::arg("offset"), py::arg("want_lr"), py::arg("divisor") = 0.0);
   m.def("rlr_vote", &rlr_vote);
-  m.def("agg_avg", &agg_avg);
+  m.def("agg_avg", &agg_avg, py::arg("U"), py::arg("w"),
+        py::arg("divisor") = 0.0);
   m.def("agg_sign", &agg_sign);
   m.def("agg_comed", &agg_comed);
   m.def("apply_update", &apply_update);
@@ -1681,6 +1760,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("pairdist_max_k", &pairdist_max_k);
   m.def("pairdist_chunks", &pairdist_chunks);
   m.def("pairdist_ws_doubles", &pairdist_ws_doubles);
+  m.def("rows_add_", &rows_add_);
+  m.def("gram_rows", &gram_rows);
+  m.def("foolsgold_weights", &foolsgold_weights);
+  m.def("foolsgold_max_k", &foolsgold_max_k);
   m.def("geomed_sqdist", &geomed_sqdist);
   m.def("geomed_weights", &geomed_weights);
   m.def("geomed_max_k", &geomed_max_k);

@@ -276,6 +276,26 @@ int pairdist_chunks(int K, long n);
 long pairdist_ws_doubles(int K, long n);
 void launch_pairwise_sqdist(const double* U, int K, long n, double* ws,
                             double* D, void* s);
+// The same stages 1 and 2 over the rows rows[0..K) of H (any number of rows,
+// n columns): G (K, K), G[i][j] = <H[rows[i]], H[rows[j]]>, exactly
+// symmetric.  rows: K int64 on the device, every entry a valid row of H (the
+// caller checks; the kernel dereferences them as given).  Same chunking and
+// workspace as launch_pairwise_sqdist.
+void launch_gram_rows(const double* H, const long* rows, int K, long n,
+                      double* ws, double* G, void* s);
+// foolsgold.hip.  launch_rows_add: H[rows[k]][j] += U[k][j] for the K
+// DISTINCT valid rows rows[0..K) of H (int64 on the device), any K >= 1.
+// launch_foolsgold_weights: FoolsGold's weights from the Gram matrix G (K, K)
+// of the sampled history rows, 1 <= K <= foolsgold_max_k(): cs (K, K) the
+// cosine matrix with a zero diagonal (before pardoning), alpha (K) the
+// learning-rate weights in [0, 1].  Three small launches, no host
+// synchronisation, no workspace: alpha and the diagonal of cs carry the row
+// maxima between the launches.
+int foolsgold_max_k();
+void launch_rows_add(double* H, const long* rows, const double* U, int K,
+                     long n, void* s);
+void launch_foolsgold_weights(const double* G, int K, double kappa,
+                              double* cs, double* alpha, void* s);
 // geomed.hip: smoothed Weiszfeld iterations for the geometric median of the
 // rows of U (K, n), 1 <= K <= geomed_max_k().  Stage 1 splits n into
 // geomed_chunks(K, n) <= 512 chunks (a pure function of K and n) and writes

@@ -46,6 +46,12 @@
 // (G_ii + G_jj) - 2 G_ij and writes D[i][j] and D[j][i] from the one value.
 // G lives in the workspace behind the partials.
 //
+// launch_gram_rows is stages 1 and 2 over the rows rows[0..K) of a taller
+// matrix H (FoolsGold's per-agent history) and a finish that writes G itself,
+// mirrored from the one reduced value (pairdist_gram_finish_k): the partial
+// kernels are templated on the row map, so the distance path compiles
+// without it.  A pure function of (H, rows).
+//
 // The chunking depends on (K, n) only: pairdist_chunks().  chunks * pairs
 // <= kPdTargetBlocks = 1024 = four resident blocks per CU (128 VGPRs,
 // 34 KiB LDS), all in flight at once and none left over for a ragged second
@@ -101,11 +107,17 @@ __device__ inline void pd_pair_decode(int p, int T, int& ti, int& tj) {
   tj = ti + p;
 }
 
+// kMap: row r of the operand is row rows[r] of U (launch_gram_rows); without
+// it rows is unused and the kernel is the one launch_pairwise_sqdist always
+// had.  The mapped row offsets of both tiles are staged in LDS once: a slab
+// load reads them back as a broadcast.
+template <bool kMap>
 __global__ __launch_bounds__(256) void pairdist_partial_k(
-    const double* __restrict__ U, int K, long n, int T, int pairs,
-    long chunk_len, double* __restrict__ ws) {
+    const double* __restrict__ U, const long* __restrict__ rows, int K,
+    long n, int T, int pairs, long chunk_len, double* __restrict__ ws) {
   __shared__ double sA[kPdTile * kPdStride];
   __shared__ double sB[kPdTile * kPdStride];
+  __shared__ long sRow[kMap ? 2 * kPdTile : 1];
   const int p = blockIdx.x % pairs;
   const long c = blockIdx.x / pairs;
   int ti, tj;
@@ -134,6 +146,14 @@ __global__ __launch_bounds__(256) void pairdist_partial_k(
                    !(diag && ra > cb);
     }
 
+  if constexpr (kMap) {
+    if (tid < 2 * kPdTile) {
+      const int r = (tid < kPdTile ? ti : tj) * kPdTile + (tid & (kPdTile - 1));
+      sRow[tid] = r < K ? rows[r] * n : 0;
+    }
+    __syncthreads();
+  }
+
   double ga[8], gb[8];
   auto gload = [&](long cb) {
     const long col = cb + lc;
@@ -141,8 +161,14 @@ __global__ __launch_bounds__(256) void pairdist_partial_k(
     for (int i = 0; i < 8; ++i) {
       const int row = lr + 8 * i;
       const int ia = ti * kPdTile + row, ib = tj * kPdTile + row;
-      ga[i] = (ia < K && col < col1) ? U[(long)ia * n + col] : 0.0;
-      gb[i] = (!diag && ib < K && col < col1) ? U[(long)ib * n + col] : 0.0;
+      if constexpr (kMap) {
+        ga[i] = (ia < K && col < col1) ? U[sRow[row] + col] : 0.0;
+        gb[i] = (!diag && ib < K && col < col1)
+                    ? U[sRow[kPdTile + row] + col] : 0.0;
+      } else {
+        ga[i] = (ia < K && col < col1) ? U[(long)ia * n + col] : 0.0;
+        gb[i] = (!diag && ib < K && col < col1) ? U[(long)ib * n + col] : 0.0;
+      }
     }
   };
 
@@ -200,9 +226,10 @@ __global__ __launch_bounds__(256) void pairdist_partial_k(
 }
 
 // K <= 16: one 16-row tile, chunk c -> ws[c][16][16]
+template <bool kMap>
 __global__ __launch_bounds__(256) void pairdist_partial16_k(
-    const double* __restrict__ U, int K, long n, long chunk_len,
-    double* __restrict__ ws) {
+    const double* __restrict__ U, const long* __restrict__ rows, int K,
+    long n, long chunk_len, double* __restrict__ ws) {
   __shared__ double sA[kPdSmallK * kPdSmallStride];
   __shared__ double red[4 * kPdSmallK * kPdSmallK];
   const long c = blockIdx.x;
@@ -217,13 +244,26 @@ __global__ __launch_bounds__(256) void pairdist_partial16_k(
   const int fr = lane & 15;
   const int fk = lane >> 4;
 
+  // kMap: the 8 rows this thread loads, as offsets into U
+  long off[8];
+  if constexpr (kMap) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int row = lr + 2 * i;
+      off[i] = row < K ? rows[row] * n : 0;
+    }
+  }
+
   double ga[8];
   auto gload = [&](long cb) {
     const long col = cb + lc;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int row = lr + 2 * i;
-      ga[i] = (row < K && col < col1) ? U[(long)row * n + col] : 0.0;
+      if constexpr (kMap)
+        ga[i] = (row < K && col < col1) ? U[off[i] + col] : 0.0;
+      else
+        ga[i] = (row < K && col < col1) ? U[(long)row * n + col] : 0.0;
     }
   };
 
@@ -325,6 +365,46 @@ __global__ __launch_bounds__(256) void pairdist_finish_k(
   }
 }
 
+// The Gram matrix itself from the reduced slabs: one block per tile pair
+// writes Gm[i][j] and Gm[j][i] from the one reduced value, and the diagonal
+// from the diagonal pair.
+__global__ __launch_bounds__(256) void pairdist_gram_finish_k(
+    const double* __restrict__ G, int K, int T, int side,
+    double* __restrict__ Gm) {
+  const int p = blockIdx.x;
+  const long slab = (long)side * side;
+  int ti, tj;
+  pd_pair_decode(p, T, ti, tj);
+  for (int e = threadIdx.x; e < (int)slab; e += 256) {
+    const int li = e / side, lj = e % side;
+    const int i = ti * side + li, j = tj * side + lj;
+    if (i >= K || j >= K) continue;
+    if (ti == tj && li > lj) continue;  // (i, j) is written by its mirror
+    const double g = G[(long)p * slab + e];
+    Gm[(long)i * K + j] = g;
+    if (i != j) Gm[(long)j * K + i] = g;
+  }
+}
+
+// stages 1 and 2; returns the reduced slabs, which live behind the partials
+template <bool kMap>
+static double* pd_gram_slabs(const double* U, const long* rows, int K, long n,
+                             double* ws, hipStream_t st) {
+  const int T = pd_tiles(K), pairs = pd_pairs(K);
+  const int chunks = pairdist_chunks(K, n);
+  if (K <= kPdSmallK)
+    pairdist_partial16_k<kMap><<<chunks, 256, 0, st>>>(
+        U, rows, K, n, pd_chunk_len(K, n), ws);
+  else
+    pairdist_partial_k<kMap><<<chunks * pairs, 256, 0, st>>>(
+        U, rows, K, n, T, pairs, pd_chunk_len(K, n), ws);
+  const int side = pd_slab_side(K);
+  double* G = ws + (long)chunks * pairs * side * side;
+  pairdist_reduce_k<<<pairs * (side * side / 16), 256, 0, st>>>(
+      ws, K, T, pairs, chunks, side, G);
+  return G;
+}
+
 extern "C" {
 int pairdist_max_k() { return kPairdistMaxK; }
 
@@ -342,18 +422,16 @@ long pairdist_ws_doubles(int K, long n) {
 void launch_pairwise_sqdist(const double* U, int K, long n, double* ws,
                             double* D, void* s) {
   hipStream_t st = (hipStream_t)s;
-  const int T = pd_tiles(K), pairs = pd_pairs(K);
-  const int chunks = pairdist_chunks(K, n);
-  if (K <= kPdSmallK)
-    pairdist_partial16_k<<<chunks, 256, 0, st>>>(U, K, n,
-                                                 pd_chunk_len(K, n), ws);
-  else
-    pairdist_partial_k<<<chunks * pairs, 256, 0, st>>>(
-        U, K, n, T, pairs, pd_chunk_len(K, n), ws);
-  const int side = pd_slab_side(K);
-  double* G = ws + (long)chunks * pairs * side * side;
-  pairdist_reduce_k<<<pairs * (side * side / 16), 256, 0, st>>>(
-      ws, K, T, pairs, chunks, side, G);
-  pairdist_finish_k<<<pairs, 256, 0, st>>>(G, K, T, side, D);
+  const double* G = pd_gram_slabs<false>(U, nullptr, K, n, ws, st);
+  pairdist_finish_k<<<pd_pairs(K), 256, 0, st>>>(G, K, pd_tiles(K),
+                                                 pd_slab_side(K), D);
+}
+
+void launch_gram_rows(const double* H, const long* rows, int K, long n,
+                      double* ws, double* Gm, void* s) {
+  hipStream_t st = (hipStream_t)s;
+  const double* G = pd_gram_slabs<true>(H, rows, K, n, ws, st);
+  pairdist_gram_finish_k<<<pd_pairs(K), 256, 0, st>>>(G, K, pd_tiles(K),
+                                                      pd_slab_side(K), Gm);
 }
 }

@@ -33,9 +33,9 @@ def args_parser(argv=None):
                         help="number of communication rounds R")
     parser.add_argument('--aggr', type=str, default='avg',
                         choices=['avg', 'comed', 'sign', 'trmean', 'krum',
-                                 'geomed', 'bulyan'],
-                        help="aggregation rule (trmean, krum, geomed and "
-                             "bulyan are build additions)")
+                                 'geomed', 'bulyan', 'foolsgold'],
+                        help="aggregation rule (trmean, krum, geomed, bulyan "
+                             "and foolsgold are build additions)")
     parser.add_argument('--local_ep', type=int, default=2,
                         help="number of local epochs E")
     parser.add_argument('--bs', type=int, default=256,
@@ -89,6 +89,9 @@ def args_parser(argv=None):
     parser.add_argument('--geomed_nu', type=float, default=1e-6,
                         help="smoothing: a weight is 1 / max(nu, distance) "
                              "(--aggr geomed)")
+    parser.add_argument('--foolsgold_kappa', type=float, default=1.0,
+                        help="confidence of the logit that turns similarity "
+                             "into a weight, > 0 (--aggr foolsgold)")
     parser.add_argument('--server_clip', type=float, default=0,
                         help="server-side bound on each update's L2 norm "
                              "before aggregation (0 disables)")
@@ -147,6 +150,12 @@ def check_geomed(iters, nu):
         raise ValueError(f"--geomed_nu must be > 0, got {nu}")
 
 
+def check_foolsgold(kappa):
+    """Likewise for --aggr foolsgold."""
+    if not 0 < kappa < float('inf'):
+        raise ValueError(f"--foolsgold_kappa must be > 0, got {kappa}")
+
+
 def check_server_clip(value, mode):
     """Likewise for the server-side norm clip."""
     if not value >= 0:
@@ -163,7 +172,7 @@ def finalize_args(args):
     value per coordinate survives the trim for every K; krum_f, krum_m >= 0
     (their upper limits depend on the sampled K and are checked by the
     server); bulyan_f >= 0 (K >= 4 bulyan_f + 3 likewise by the server);
-    geomed_iters >= 0 and geomed_nu > 0; server_clip >= 0 with a known mode;
+    geomed_iters >= 0 and geomed_nu > 0; foolsgold_kappa > 0; server_clip >= 0 with a known mode;
     attack_boost > 0."""
     args.server_lr = args.server_lr if args.aggr == 'sign' else 1.0
     if not 0 <= args.trim_frac < 0.5:
@@ -176,6 +185,7 @@ def finalize_args(args):
     if args.bulyan_f < 0:
         raise ValueError(f"--bulyan_f must be >= 0, got {args.bulyan_f}")
     check_geomed(args.geomed_iters, args.geomed_nu)
+    check_foolsgold(args.foolsgold_kappa)
     check_server_clip(args.server_clip, args.server_clip_mode)
     if not 0 < args.attack_boost < float('inf'):
         raise ValueError(

@@ -3,7 +3,8 @@ federated.py:95), defined by this build:
 
 one file per snap round containing the flat fp32 parameter vector (+ flat
 float buffers for BN models), the round index, the full arg namespace, the
-master seed, and cum_poison_acc_mean.  Every RNG stream is derived
+master seed, and cum_poison_acc_mean; under --aggr foolsgold also the
+server's (num_agents, n) fp64 history, as 'server_state'.  Every RNG stream is derived
 statelessly from (seed, purpose, round/agent/...), so no RNG state needs
 saving and a checkpoint written at any world size resumes at any other
 world size bit-identically."""
@@ -15,7 +16,11 @@ import torch
 FORMAT_VERSION = 1
 
 
-def save_checkpoint(path, global_model, rnd, args, cum_poison_acc_mean):
+def save_checkpoint(path, global_model, rnd, args, cum_poison_acc_mean,
+                    server_state=None):
+    """server_state: what the aggregation server carries across rounds
+    (Aggregation.state_dict()), stored under 'server_state' only when it is
+    not empty, so a rule without state writes the file it always wrote."""
     state = {
         'version': FORMAT_VERSION,
         'round': rnd,
@@ -26,6 +31,9 @@ def save_checkpoint(path, global_model, rnd, args, cum_poison_acc_mean):
     }
     if global_model.n_buffers:
         state['buffers'] = global_model.flat_buffers.detach().float().cpu()
+    if server_state:
+        state['server_state'] = {k: v.detach().cpu()
+                                 for k, v in server_state.items()}
     tmp = path + '.tmp'
     torch.save(state, tmp)
     os.replace(tmp, path)

@@ -8,8 +8,8 @@ from time import ctime
 
 def run_name(args):
     """Reference federated.py:27-30 run-name string; the trimmed mean, krum,
-    geomed and bulyan (build additions) append their own flags, every other
-    rule keeps the reference name byte for byte.  Server-side clipping and the
+    geomed, bulyan and foolsgold (build additions) append their own flags,
+    every other rule keeps the reference name byte for byte.  Server-side clipping and the
     attack boost (build additions) append theirs only when switched on."""
     name = (f"time:{ctime()}-clip_val:{args.clip}-noise_std:{args.noise}"
             f"-aggr:{args.aggr}-s_lr:{args.server_lr}-num_cor:{args.num_corrupt}"
@@ -23,6 +23,8 @@ def run_name(args):
         name += f"-gm_iters:{args.geomed_iters}-gm_nu:{args.geomed_nu}"
     if args.aggr == 'bulyan':
         name += f"-bulyan_f:{args.bulyan_f}"
+    if args.aggr == 'foolsgold':
+        name += f"-fg_kappa:{args.foolsgold_kappa}"
     if getattr(args, 'server_clip', 0) > 0:
         name += f"-sclip:{args.server_clip}-{args.server_clip_mode}"
     if getattr(args, 'attack_boost', 1.0) != 1.0:
@@ -40,6 +42,14 @@ def build_writer(args):
     return SummaryWriter(f"{args.log_dir}/{run_name(args)}")
 
 
+def foolsgold_history_bytes(args):
+    """8 * num_agents * n_params: what --aggr foolsgold keeps on the device
+    across rounds."""
+    from ..models import get_model
+    model = get_model(args.data, getattr(args, 'model', None))
+    return 8 * args.num_agents * sum(p.numel() for p in model.parameters())
+
+
 def print_exp_details(args):
     """Reference utils.py:287-303."""
     print('======================================')
@@ -55,6 +65,9 @@ def print_exp_details(args):
               f'{args.geomed_nu}')
     if args.aggr == 'bulyan':
         print(f'    Bulyan f: {args.bulyan_f}')
+    if args.aggr == 'foolsgold':
+        print(f'    FoolsGold kappa: {args.foolsgold_kappa} (history '
+              f'{foolsgold_history_bytes(args) / 1e6:.0f} MB)')
     if getattr(args, 'server_clip', 0) > 0:
         print(f'    Server Clip: {args.server_clip} '
               f'({args.server_clip_mode})')
