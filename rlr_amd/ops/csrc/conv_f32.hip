@@ -1339,8 +1339,12 @@ int conv_bwd_weight_splitk(int Kout, int Ncrs, long Kdim) {
 // instead of the split-K implicit GEMM: at most kSmallBwdwMaxChunks
 // m-chunks, each writing one Kout*Ncrs slab of partials.
 constexpr int kSmallBwdwMaxChunks = 2048;
+// Kout % 4 == 0: conv_small_bwdw_k stages dy as float4s that must not
+// straddle two pixels (at Kout = 10 the values of pixel m + 1 landed in
+// rows 10, 11 of pixel m; at Kout = 63 the writes left dy_lds).  Other
+// Kout take the implicit GEMM, which handles Kout tails.
 static bool conv_bwdw_small(int Kout, int Ncrs) {
-  return Ncrs <= 32 && Kout <= 64;
+  return Ncrs <= 32 && Kout <= 64 && (Kout % 4) == 0;
 }
 
 // Workspace of launch_conv_bwd_weight: the chunk partials of the small
