@@ -1809,6 +1809,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // the split-K pickers and the workspace size (in floats) each op
   // allocates for its launcher
   m.def("gemm_f32_splitk", &gemm_f32_splitk);
+  m.def("gemm_f32_shortk_tiles", &gemm_f32_shortk_tiles);
   m.def("conv_bwd_weight_splitk", &conv_bwd_weight_splitk);
   m.def("conv_bwd_weight_bf16_splitk", &conv_bwd_weight_bf16_splitk);
   m.def("conv_db_chunks", &conv_db_chunks);

@@ -245,6 +245,235 @@ void gemm_f32_k(const float* __restrict__ A, const float* __restrict__ B,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Short-K form: a chunk of at most T K-tiles (fc1: 4 or 5 per block).  The
+// pipeline above keeps one K-tile in flight, which suits the conv-sized K
+// loops; with 3..5 tiles it exposes nearly every memory latency and there is
+// no second block on the CU to hide them.  Here every global load of the
+// chunk is issued before the first LDS write, into a register ring of one
+// float4 set per tile; the same double-buffered LDS ring then consumes the
+// sets in order, and the compiler's counted s_waitcnt vmcnt(n) makes tile i
+// wait for tile i's loads only.  Same tile, wave grid, LDS image, chunking
+// and k order as gemm_f32_k, so C and every slab carry the same bits.
+//
+// For the counted waits to survive code generation the loads must be
+// unconditional and the tile count a compile-time constant: a load under a
+// branch merges to vmcnt(0) at the join.  So (a) the body is instantiated
+// per tile count NT and the kernel picks one by the block-uniform count, and
+// (b) an out-of-range float4 is loaded from the matrix base instead (always
+// mapped) and zeroed by a select at LDS-write time.  Only a float4 that
+// straddles the edge (ld % 4 == 0 but the extent is not) takes a branch,
+// which re-loads it element-wise as gemm_f32_k does.
+// ---------------------------------------------------------------------------
+constexpr int kShortKMaxTiles = 5;
+
+// One float4 slot: elements v0..v0+3 of row `row` of P, valid while
+// row_ok && v < lim.  sk_load issues the load, sk_mask (at LDS-write time)
+// zero-fills what the guards exclude.
+__device__ __forceinline__ float4 sk_load(const float* __restrict__ P,
+                                          long row, long ld, long v0,
+                                          bool row_ok, long lim) {
+  const bool full = row_ok && v0 + 3 < lim;
+  float4 q = *(const float4*)(P + (full ? row * ld + v0 : 0));
+  if (row_ok && !full && v0 < lim) {
+    const float* r = P + row * ld + v0;
+    q.x = r[0];
+    q.y = v0 + 1 < lim ? r[1] : 0.f;
+    q.z = v0 + 2 < lim ? r[2] : 0.f;
+    q.w = 0.f;
+  }
+  return q;
+}
+
+__device__ __forceinline__ float4 sk_mask(float4 q, bool row_ok, long v0,
+                                          long lim) {
+  const bool keep = row_ok && v0 < lim;
+  return {keep ? q.x : 0.f, keep ? q.y : 0.f, keep ? q.z : 0.f,
+          keep ? q.w : 0.f};
+}
+
+// The chunk [k_lo, k_hi) of exactly NT K-tiles, accumulated into acc.
+template <int NT, bool AT, bool BT>
+__device__ __forceinline__ void shortk_chunk(
+    const float* __restrict__ A, const float* __restrict__ B, int M, int N,
+    int lda, int ldb, int m_blk, int n_blk, long k_lo, long k_hi,
+    float (&A_lds)[2][BM * LDA_S], float (&B_lds)[2][BK * LDB_S],
+    f32x4 (&acc)[4][2]) {
+  const int t = threadIdx.x;
+  const int wave = t >> 6, lane = t & 63;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int l15 = lane & 15, l4 = lane >> 4;
+  // staging coordinates of gemm_f32_k: A slot j is row a_r + 32 j (NN) or
+  // m base a_v + 32 j (AT); B slot j is k row b_r + 16 j (NN) or n row
+  // b_r + 32 j (BT)
+  const int a_r = t >> 3, a_v = (t & 7) * 4;
+  const int b_r = BT ? t >> 3 : t >> 4;
+  const int b_v = BT ? (t & 7) * 4 : (t & 15) * 4;
+
+  float4 ra[NT][4], rb[NT][2];
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const long k0 = k_lo + i * BK;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (AT)
+        ra[i][j] = sk_load(A, k0 + a_r, lda, m_blk + a_v + j * 32,
+                           k0 + a_r < k_hi, M);
+      else
+        ra[i][j] = sk_load(A, m_blk + a_r + j * 32, lda, k0 + a_v,
+                           m_blk + a_r + j * 32 < M, k_hi);
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (BT)
+        rb[i][j] = sk_load(B, n_blk + b_r + j * 32, ldb, k0 + b_v,
+                           n_blk + b_r + j * 32 < N, k_hi);
+      else
+        rb[i][j] = sk_load(B, k0 + b_r + j * 16, ldb, n_blk + b_v,
+                           k0 + b_r + j * 16 < k_hi, N);
+    }
+  }
+
+#pragma unroll
+  for (int i = 0; i <= NT; ++i) {
+    // first half of tile i - 1's MFMAs, the LDS write of tile i, the second
+    // half: the wait for tile i's loads sits under tile i - 1's MFMAs
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      if (i > 0) {
+        const float* Abuf = A_lds[(i - 1) & 1];
+        const float* Bbuf = B_lds[(i - 1) & 1];
+#pragma unroll
+        for (int kk = half * (BK / 8); kk < (half + 1) * (BK / 8); ++kk) {
+          float a_frag[4], b_frag[2];
+#pragma unroll
+          for (int mi = 0; mi < 4; ++mi)
+            a_frag[mi] =
+                Abuf[(wr * 64 + mi * 16 + l15) * LDA_S + kk * 4 + l4];
+#pragma unroll
+          for (int ni = 0; ni < 2; ++ni)
+            b_frag[ni] =
+                Bbuf[(kk * 4 + l4) * LDB_S + wc * 32 + ni * 16 + l15];
+#pragma unroll
+          for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+              acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                  a_frag[mi], b_frag[ni], acc[mi][ni], 0, 0, 0);
+        }
+      }
+      if (half == 0 && i < NT) {
+        const long k0 = k_lo + i * BK;
+        float* Aw = A_lds[i & 1];
+        float* Bw = B_lds[i & 1];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (AT) {
+            const float4 q = sk_mask(ra[i][j], k0 + a_r < k_hi,
+                                     m_blk + a_v + j * 32, M);
+            const float v[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              Aw[(a_v + j * 32 + e) * LDA_S + a_r] = v[e];
+          } else {
+            const float4 q = sk_mask(ra[i][j], m_blk + a_r + j * 32 < M,
+                                     k0 + a_v, k_hi);
+            float* dst = &Aw[(a_r + j * 32) * LDA_S + a_v];
+            ((float2*)dst)[0] = {q.x, q.y};
+            ((float2*)dst)[1] = {q.z, q.w};
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          if (BT) {
+            const float4 q = sk_mask(rb[i][j], n_blk + b_r + j * 32 < N,
+                                     k0 + b_v, k_hi);
+            const float v[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              Bw[(b_v + e) * LDB_S + b_r + j * 32] = v[e];
+          } else {
+            const float4 q = sk_mask(rb[i][j], k0 + b_r + j * 16 < k_hi,
+                                     n_blk + b_v, N);
+            *(float4*)&Bw[(b_r + j * 16) * LDB_S + b_v] = q;
+          }
+        }
+      }
+    }
+    // tile i is in LDS for everyone; everyone is done reading tile i - 1
+    if (i < NT) __syncthreads();
+  }
+}
+
+// picks the instantiation of the block's tile count: nt in [0, NT]
+template <int NT, bool AT, bool BT, typename... Args>
+__device__ __forceinline__ void shortk_dispatch(int nt, Args&&... args) {
+  if (nt == NT) {
+    shortk_chunk<NT, AT, BT>(args...);
+  } else if constexpr (NT > 1) {
+    shortk_dispatch<NT - 1, AT, BT>(nt, args...);
+  }
+}
+
+// Requires lda % 4 == 0 && ldb % 4 == 0 (gemm_f32_k's VEC) and
+// k_per_chunk <= T * BK; arguments, grid, slab layout and epilogue are
+// gemm_f32_k's.
+template <int T, bool AT, bool BT>
+__global__ __launch_bounds__(256)
+void gemm_f32_shortk_k(const float* __restrict__ A,
+                       const float* __restrict__ B, float* __restrict__ C,
+                       const float* __restrict__ bias, int M, int N, int K,
+                       int lda, int ldb, int ldc, long k_per_chunk, int relu,
+                       int direct_out) {
+  __shared__ float A_lds[2][BM * LDA_S];
+  __shared__ float B_lds[2][BK * LDB_S];
+
+  const int m_blk = blockIdx.x * BM;
+  const int n_blk = blockIdx.y * BN;
+  const long k_lo = (long)blockIdx.z * k_per_chunk;
+  const long k_hi = min((long)K, k_lo + k_per_chunk);
+  // block-uniform: a shorter last chunk and the empty chunks of a deep
+  // split (which still write their zero slab) run a smaller instantiation
+  const int nt = k_hi > k_lo ? (int)((k_hi - k_lo + BK - 1) / BK) : 0;
+
+  f32x4 acc[4][2];
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = {0.f, 0.f, 0.f, 0.f};
+
+  shortk_dispatch<T, AT, BT>(nt, A, B, M, N, lda, ldb, m_blk, n_blk, k_lo,
+                             k_hi, A_lds, B_lds, acc);
+
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = t >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int l15 = lane & 15, l4 = lane >> 4;
+  // the output: C itself or this chunk's slab, [M][ldo]
+  const int ldo = direct_out ? ldc : N;
+  float* __restrict__ O = direct_out ? C : C + (long)blockIdx.z * M * N;
+  // epilogue: C/D mapping col = lane&15, row = (lane>>4)*4 + reg
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi) {
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      int col = n_blk + wc * 32 + ni * 16 + l15;
+      if (col >= N) continue;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int row = m_blk + wr * 64 + mi * 16 + l4 * 4 + r;
+        if (row >= M) continue;
+        float v = acc[mi][ni][r];
+        if (direct_out) {
+          if (bias) v += bias[col];
+          if (relu) v = fmaxf(v, 0.f);
+        }
+        O[(long)row * ldo + col] = v;
+      }
+    }
+  }
+}
+
 // fixed-order split-K reduce + bias + relu.  Two geometries:
 //  * small outputs / large SK: one WAVE per output, lanes over z + shuffle
 //    tree (the serial-z loop was pure L2-latency, 60 us for 288 outputs)
@@ -358,8 +587,52 @@ long gemm_splitk_ws_floats(int M, int N, int SK) {
   return (long)(SK + splitk_stage1_slabs(SK)) * M * N;
 }
 
+// launch_gemm_f32_main's tiny-problem branch: one direct kernel, no tiles
+static bool gemm_f32_tiny(int M, int N, int K) {
+  return (long)M * N * K <= 8'000'000 && (long)M * N <= 65536;
+}
+
+// The K-tiles per chunk when launch_gemm_f32_main runs the short-K form,
+// else 0: the call takes the tile path, both row strides allow float4
+// loads, and a full chunk holds 3..kShortKMaxTiles K-tiles.  (A two-tile
+// chunk has at most one latency to lose in gemm_f32_k.)  Host arithmetic
+// only; RLR_AMD_NO_GEMM_SHORTK is the launcher's business, not this
+// function's.
+int gemm_f32_shortk_tiles(int M, int N, int K, int SK, int lda, int ldb) {
+  if (gemm_f32_tiny(M, N, K)) return 0;
+  if (lda % 4 != 0 || ldb % 4 != 0) return 0;
+  long k_per_chunk = SK == 1 ? (long)K
+                             : ((((long)K + SK - 1) / SK + BK - 1) / BK) * BK;
+  if (k_per_chunk <= 2 * BK || k_per_chunk > kShortKMaxTiles * BK) return 0;
+  return (int)((k_per_chunk + BK - 1) / BK);
+}
+
+// the short-K launches of launch_gemm_f32_main, same arguments
+static void launch_gemm_f32_shortk(const float* A, const float* B, float* out,
+                                   const float* bias, int M, int N, int K,
+                                   int lda, int ldb, int ldc, dim3 grid,
+                                   long k_per_chunk, int relu, int direct_out,
+                                   int layout, hipStream_t st) {
+  constexpr int T = kShortKMaxTiles;
+  if (layout == 1)
+    gemm_f32_shortk_k<T, true, false><<<grid, 256, 0, st>>>(
+        A, B, out, bias, M, N, K, lda, ldb, ldc, k_per_chunk, relu,
+        direct_out);
+  else if (layout == 2)
+    gemm_f32_shortk_k<T, false, true><<<grid, 256, 0, st>>>(
+        A, B, out, bias, M, N, K, lda, ldb, ldc, k_per_chunk, relu,
+        direct_out);
+  else
+    gemm_f32_shortk_k<T, false, false><<<grid, 256, 0, st>>>(
+        A, B, out, bias, M, N, K, lda, ldb, ldc, k_per_chunk, relu,
+        direct_out);
+}
+
 // ws: null unless SK>1, then gemm_splitk_ws_floats(M, N, SK) floats.
 // layout: 0 = NN, 1 = A transposed ([K][M]), 2 = B transposed ([N][K]).
+// A chunk of 3..5 K-tiles with float4-able strides runs the short-K form
+// (gemm_f32_shortk_tiles) unless RLR_AMD_NO_GEMM_SHORTK=1, which is read on
+// every call and sends everything to gemm_f32_k.
 // The main kernel only.  Returns 1 when it left SK partial slabs in ws that
 // launch_splitk_reduce (or the roles of splitk_reduce_roles) must still
 // fold into C, 0 when C is complete.
@@ -370,7 +643,7 @@ int launch_gemm_f32_main(const float* A, const float* B, float* C,
   hipStream_t st = (hipStream_t)s;
   // tiny problems: one direct kernel beats tile GEMM + split-K reduce;
   // with a real K give every output a wave (lane-strided K + shuffle)
-  if ((long)M * N * K <= 8'000'000 && (long)M * N <= 65536) {
+  if (gemm_f32_tiny(M, N, K)) {
     if (K >= 32) {
       int wpb = kBlock / kWave;
       gemm_small_wave_k<<<((long)M * N + wpb - 1) / wpb, kBlock, 0, st>>>(
@@ -386,6 +659,13 @@ int launch_gemm_f32_main(const float* A, const float* B, float* C,
                              : ((((long)K + SK - 1) / SK + BK - 1) / BK) * BK;
   bool vec = (lda % 4 == 0) && (ldb % 4 == 0);
   float* out = SK == 1 ? C : ws;
+  const char* no_shortk = getenv("RLR_AMD_NO_GEMM_SHORTK");
+  if (!(no_shortk && no_shortk[0] == '1') &&
+      gemm_f32_shortk_tiles(M, N, K, SK, lda, ldb)) {
+    launch_gemm_f32_shortk(A, B, out, bias, M, N, K, lda, ldb, ldc, grid,
+                           k_per_chunk, relu, SK == 1, layout, st);
+    return SK > 1;
+  }
   if (layout == 1) {
     if (vec)
       gemm_f32_k<true, true, false><<<grid, 256, 0, st>>>(

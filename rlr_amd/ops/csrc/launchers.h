@@ -333,6 +333,9 @@ void launch_rowclip(double* U, int K, long n, double value, int median_mode,
 // gemm_f32.hip
 int gemm_f32_splitk(int M, int N, int K);
 long gemm_splitk_ws_floats(int M, int N, int SK);
+// K-tiles per chunk (3..5) when launch_gemm_f32_main runs the short-K form
+// of the tile kernel for this call at split depth SK, else 0
+int gemm_f32_shortk_tiles(int M, int N, int K, int SK, int lda, int ldb);
 // the GEMM without its split-K combine: returns 1 when ws holds SK partial
 // slabs that still have to be folded into C, 0 when C is complete
 int launch_gemm_f32_main(const float* A, const float* B, float* C,
